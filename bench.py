@@ -15,11 +15,28 @@ element, its wave-wide reductions as butterflies and its pivot square roots /
 reciprocals at hardware precision -- within north_star's 1e-4 relative L2 of
 the reference (measured 1.2e-5 against its strict build, 1.6e-5 against its
 default build, which is itself 1.2e-5 from the strict one;
-tests/test_gpu_fast_fit.py pins exactly this configuration at 4K) -- and the exact path (bit-exact to the reference's
-strict build, the library's default) as `ms_per_frame_exact` beside it
-(--fit exact swaps the two).
+tests/test_gpu_fast_fit.py pins exactly this configuration at 4K); --fit
+exact times the exact path instead (bit-exact to the reference's strict
+build, the library's default).
 
-The N = 1 line also carries the metric's other sizes, untiled on the same
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what that
+headline needs and no more: it renders the frames, spins the clock up, runs
+the W warm-up and the K timed frames and prints the line (`value` =
+`ms_per_step` = wall-clock ms per timed frame, with K1's and K2's HIP-event
+times from every 10th timed frame and K1's roofline, which cost no run of
+their own).  --dump-outputs DIR then writes what the timed path left after
+its last frame -- the TAA output copy_output returns -- as DIR/output.npy
+(float32 (pixels, 3); of a frame of more than 2^22 pixels the same seeded
+2^22 of them every run).  The inputs depend on the arguments alone (--seed),
+and the kernels have no run-to-run freedom, so two builds can be compared
+value for value.  A run of more frames than fit in 64 GiB of rendered inputs
+keeps a window of the sequence resident and stops the clock while the next
+window is rendered: the K timed frames are the same frames either way.
+
+Everything else is behind --full.  With it the N = 1 line also carries
+`psnr_db` (against the clean render), the other fit as `ms_per_frame_exact`
+(or, with --fit exact, `ms_per_frame_fast_fit`), the metric's other sizes,
+untiled on the same
 GPU: `ms_per_frame_1080p` (1920x1080) and `ms_per_frame_8k` (7680x4320, the
 1-GPU point of the north star's scaling target); BASELINE's other 4K
 configurations with their own rooflines: `ms_per_frame_cfg5` (config 5:
@@ -49,7 +66,7 @@ frame is one launch (K1 blocks, then the frame's TAA tiles, include/bmfr.h
 bmfr_sizes.frame_launches) and the timed frames run with nothing between
 their launches (an event between two frames costs ~5 us of GPU time at
 1080p, profiles/r06_gap_1080p.txt): two HIP events around the timed region
-give the device's frame period (`device_ms_per_frame`); an untimed pass over
+give the device's frame period (`device_ms_per_frame`); with --full an untimed pass over
 the same frames with events around each launch gives the frame kernel's
 duration (`roofline.launch_ms`, `kernel_ms.frame_one_launch`), and another
 with libbmfr's per-kernel events K1 and K2 timed as separate launches.  Larger frames (4K, 8K) are two launches, K1
@@ -60,7 +77,7 @@ Extra JSON fields: `roofline` for the dominant kernel of the timed region
 (the one-launch frame kernel, with the frame's algorithmic bytes; K1 where
 frames are not one launch), `roofline_k1` / `roofline_k2` for K1 and the TAA
 kernel timed apart (compulsory bytes: bench.k1_bytes_per_px /
-k2_bytes_per_px); `cpu_baseline` = the CPU oracle
+k2_bytes_per_px); with --full, `cpu_baseline` = the CPU oracle
 (oracle/liboracle.so, OpenMP) on a bounded sample of the same sequence.
 """
 from __future__ import annotations
@@ -111,6 +128,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: besides the headline run, everything else this benchmark measures -- the "
+                         "sequence-API, 1080p, 8K, config-5, f32-tmp_data and other-fit lines, the CPU baseline, "
+                         "PSNR against the clean render and the untimed per-kernel passes of one-launch frames "
+                         "(the --no-* flags and --cpu-frames 0 drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame's output (what copy_output returns) as "
+                         "DIR/output.npy (float32; DIR/output_rank<r>.npy for N > 1)")
     ap.add_argument("--width", type=int, default=None, help="default 3840 (N = 1), 7680 (N > 1)")
     ap.add_argument("--height", type=int, default=None, help="default 2160 (N = 1), 4320 (N > 1)")
     ap.add_argument("--half-tmp", type=int, default=1)
@@ -163,6 +188,21 @@ def parse(argv=None):
 def psnr(a: np.ndarray, b: np.ndarray) -> float:
     mse = float(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2))
     return 10 * np.log10(1.0 / mse) if mse > 0 else float("inf")
+
+
+DUMP_PIXELS = 1 << 22  # --dump-outputs: pixels written of a larger output (float3: 48 MiB)
+
+
+def sample_output(out: torch.Tensor, seed: int) -> np.ndarray:
+    """--dump-outputs: the output (float3 per pixel of the context's region)
+    as a float32 (pixels, 3) array; of more than DUMP_PIXELS pixels, the
+    same DUMP_PIXELS of them every run (drawn once from `seed`, in image
+    order)."""
+    px = out.view(-1, 3)
+    if px.shape[0] > DUMP_PIXELS:
+        idx = np.sort(np.random.default_rng(seed).choice(px.shape[0], DUMP_PIXELS, replace=False))
+        px = px[torch.from_numpy(idx).to(px.device)]
+    return px.float().cpu().numpy()
 
 
 def cpu_model() -> str:
@@ -237,6 +277,8 @@ def with_traffic(roof: dict, workload_key: str, launch_ms: float) -> dict:
 
 
 PROF_STRIDE = 10  # timed frames between two recorded with per-kernel events
+PROF_CAPACITY = 4096  # recorded frames libbmfr keeps (the last ones of a longer run)
+FRAME_POOL_BYTES = 64 << 30  # rendered input frames resident at a time (4K, f32 planes: 172 frames)
 
 
 class NativeTransport:
@@ -253,10 +295,13 @@ class NativeTransport:
         self.x.run(frame)
 
 
-def run_sequence(a, W, H, tile, grid, rank, world, dev, backend, steps, warmup, per_frame=False):
+def run_sequence(a, W, H, tile, grid, rank, world, dev, backend, steps, warmup, per_frame=False,
+                 keep_output=False):
     """Denoise frames 0..warmup+steps-1 of the synthetic W x H sequence (this
-    rank's tile of it); time the last `steps` frames.  Returns the timings,
-    per-kernel HIP-event means and the PSNR of the last output."""
+    rank's tile of it); time the last `steps` frames.  Returns the timings
+    and per-kernel HIP-event means; with --full the PSNR of the last output
+    and a one-launch frame's kernel times (untimed passes); with keep_output
+    the last output itself (sample_output)."""
     scaled = bmfr_amd.SCALED_THIRD_ORDER if a.third_order else bmfr_amd.SCALED_DEFAULT
     cfg = bmfr_amd.BmfrConfig(image_width=W, image_height=H, scaled=scaled,
                               use_half_precision_in_tmp_data=a.half_tmp,
@@ -272,17 +317,45 @@ def run_sequence(a, W, H, tile, grid, rank, world, dev, backend, steps, warmup, 
     nfr = warmup + steps
     seed = a.seed
 
-    # Render every frame's region into HBM up front (untimed).
-    frames = [bmfr_amd.synth_region_device(W, H, region, f, seed=seed, device=local) for f in range(nfr)]
-    if a.input_half:  # the planes as half3 (the f32 render rounded to nearest)
-        frames = [{k: (v.half() if k in ("noisy", "normals", "positions", "albedo") else v) for k, v in fr.items()}
-                  for fr in frames]
+    def render(f):
+        fr = bmfr_amd.synth_region_device(W, H, region, f, seed=seed, device=local)
+        if a.input_half:  # the planes as half3 (the f32 render rounded to nearest)
+            fr = {k: (v.half() if k in ("noisy", "normals", "positions", "albedo") else v) for k, v in fr.items()}
+        return fr
+
+    # Render every frame's region into HBM up front (untimed).  A run of more
+    # frames than FRAME_POOL_BYTES (or half the free memory) hold keeps a window
+    # of the sequence resident instead: the clock stops at the end of a window,
+    # the next one is rendered (frame f - 1 stays, frame f reads its normals
+    # and positions) and the clock starts again -- the same frames either way.
+    plane_bytes = 4 * 12 * region[2] * region[3]  # four float3 planes, rendered as f32
+    window = max(2, min(FRAME_POOL_BYTES, torch.cuda.mem_get_info(dev)[0] // 2) // plane_bytes)
+    if world > 1:  # the ranks stop the clock at the same frames
+        t = torch.tensor([window], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        window = int(t.item())
+    frames = {f: render(f) for f in range(min(nfr, window))}
+
+    def resident_end(f):
+        """Make frame f (and f - 1) resident; the end of the resident run of frames from f."""
+        if f not in frames:
+            torch.cuda.synchronize()  # nothing in flight reads the frames that go
+            for g in [g for g in frames if g != f - 1]:
+                del frames[g]
+            for g in range(f, min(nfr, f + window - 1)):
+                frames[g] = render(g)
+        e = f
+        while e in frames:
+            e += 1
+        return e
+
     cams = []
     for f in range(nfr):
         vp, _ = bmfr_amd.synth_camera(W, H, max(f - 1, 0))
         _, jit = bmfr_amd.synth_camera(W, H, f)
         cams.append((vp, jit))
-    scratch = spin_up(a, cfg, local, frames, cams)  # its last frames still run under the warm-up frames
+    # the scratch context's last frames still run under the warm-up frames
+    scratch = spin_up(a, cfg, local, [frames[f] for f in sorted(frames)], cams)
     transport = None
     if grid:
         # torch.distributed point-to-point (RCCL with the nccl backend; gloo, host-staged, in the
@@ -355,46 +428,57 @@ def run_sequence(a, W, H, tile, grid, rank, world, dev, backend, steps, warmup, 
     # on every PROF_STRIDE-th frame.
     one_launch = grid is None and per_frame and cfg.sizes().frame_launches == 1
     stride = PROF_STRIDE if steps >= PROF_STRIDE else 1
-    tev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if one_launch else None
+    tevs = []  # one_launch: a pair of events around each resident run of timed frames
 
     def run_range(f0, f1, timed=False):
         if pipelined:
-            den.process_sequence(frames[f0:f1], cams[f0:f1], f0)
+            den.process_sequence([frames[f] for f in range(f0, f1)], cams[f0:f1], f0)
         else:
-            if tev and timed:
+            tev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if one_launch and timed else None
+            if tev:
                 tev[0].record(compute)
             for f in range(f0, f1):
                 run(f, mark=timed and not one_launch and f % stride == 0)
-            if tev and timed:
+            if tev:
                 tev[1].record(compute)
+                tevs.append(tev)
 
-    if warmup:
-        run_range(0, warmup)
+    f = 0
+    while f < warmup:
+        f1 = min(warmup, resident_end(f))
+        run_range(f, f1)
+        f = f1
     if not one_launch:
-        den.set_profiling(True, capacity=steps, stride=stride)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    run_range(warmup, warmup + steps, timed=True)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+        den.set_profiling(True, capacity=min(steps, PROF_CAPACITY), stride=stride)
+    elapsed = 0.0
+    while f < nfr:
+        f1 = resident_end(f)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run_range(f, f1, timed=True)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed += time.perf_counter() - t0
+        f = f1
     if world > 1:
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    frame_kernel_ms = period_ms = None
+    frame_kernel_ms = period_ms = kprof = None
     if one_launch:
-        period_ms = tev[0].elapsed_time(tev[1]) / steps
+        period_ms = sum(t0.elapsed_time(t1) for t0, t1 in tevs) / steps
+    if one_launch and a.full:
         # untimed: the same frames again with events around each frame's launch
         # (the frame kernel's duration), then once more with K1 and K2 timed as
         # separate launches
         prof = bmfr_amd.Denoiser(cfg, device=local)
         fev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * steps)]
         for f in range(nfr):
+            resident_end(f)
             fr = frames[f]
             if f >= warmup:
                 fev[2 * (f - warmup)].record(compute)
@@ -404,29 +488,33 @@ def run_sequence(a, W, H, tile, grid, rank, world, dev, backend, steps, warmup, 
         torch.cuda.synchronize()
         frame_kernel_ms = float(np.mean([fev[2 * i].elapsed_time(fev[2 * i + 1]) for i in range(steps)]))
         for f in range(nfr):
+            resident_end(f)
             if f == warmup:
-                prof.set_profiling(True, capacity=steps, stride=1)
+                prof.set_profiling(True, capacity=min(steps, PROF_CAPACITY), stride=1)
             fr = frames[f]
             prof.process_frame(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"], cams[f][0], cams[f][1], f)
         torch.cuda.synchronize()
         kprof = prof.profile()
         del prof
-    else:
+    elif not one_launch:
         kprof = den.profile()
         den.set_profiling(False)
     overshoot = den.halo_status() if grid else 0  # raises if a frame reprojected past the halo
-
-    # Quality: PSNR of this rank's tile of the last output against the clean render.
-    clean = bmfr_amd.synth_region_device(W, H, region, nfr - 1, seed=seed, device=local, clean=True)["clean"]
-    out = den.copy_output(torch.empty(region[2] * region[3] * 3, device=dev))
-    torch.cuda.synchronize()
 
     def tile_of(x):
         x = x.view(region[3], region[2], 3)
         return x[tile[1] - region[1]:tile[1] - region[1] + tile[3], tile[0] - region[0]:tile[0] - region[0] + tile[2]]
 
-    last = frames[nfr - 1]
-    noisy_tm = torch.clamp(torch.clamp(last["albedo"].float() * last["noisy"].float(), min=0) ** 0.454545, 0, 1)
+    out = clean = noisy_tm = last = None
+    if a.full or keep_output:
+        out = den.copy_output(torch.empty(region[2] * region[3] * 3, device=dev))
+        torch.cuda.synchronize()
+    if a.full:
+        # Quality: PSNR of this rank's tile of the last output against the clean render.
+        clean = bmfr_amd.synth_region_device(W, H, region, nfr - 1, seed=seed, device=local, clean=True)["clean"]
+        last = frames[nfr - 1]
+        noisy_tm = torch.clamp(torch.clamp(last["albedo"].float() * last["noisy"].float(), min=0) ** 0.454545, 0, 1)
+        torch.cuda.synchronize()
     split = None
     if marks:
         mean = lambda i, j: float(np.mean([e[i].elapsed_time(e[j]) for e, _ in marks]))  # noqa: E731
@@ -442,13 +530,15 @@ def run_sequence(a, W, H, tile, grid, rank, world, dev, backend, steps, warmup, 
     res = {
         "cfg": cfg,
         "ms_per_frame": 1e3 * elapsed / steps,
-        "k1_ms": float(np.mean([p[1] for p in kprof])),
-        "k2_ms": float(np.mean([p[2] for p in kprof])),
+        # None: a one-launch frame's kernels are timed apart only by --full's untimed passes
+        "k1_ms": float(np.mean([p[1] for p in kprof])) if kprof else None,
+        "k2_ms": float(np.mean([p[2] for p in kprof])) if kprof else None,
         "dev_ms": period_ms if one_launch else float(np.mean([p[3] for p in kprof])),
         "frame_kernel_ms": frame_kernel_ms,
-        "psnr": psnr(tile_of(out).cpu().numpy(), tile_of(clean).cpu().numpy()),
-        "psnr_in": psnr(tile_of(noisy_tm).cpu().numpy(), tile_of(clean).cpu().numpy()),
+        "psnr": psnr(tile_of(out).cpu().numpy(), tile_of(clean).cpu().numpy()) if a.full else None,
+        "psnr_in": psnr(tile_of(noisy_tm).cpu().numpy(), tile_of(clean).cpu().numpy()) if a.full else None,
         "split": split,
+        "output": sample_output(out, a.seed) if keep_output else None,
     }
     if isinstance(transport, NativeTransport):
         torch.cuda.synchronize()
@@ -572,6 +662,7 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     if world > 1:
+        a.full = True  # --full is about the N = 1 line; the N > 1 lines are whole as they are
         if backend == "nccl":
             dist.init_process_group("nccl", device_id=dev)
         else:
@@ -596,7 +687,11 @@ def main():
         r1 = run_sequence(a, W, H, (0, 0, W, H), None, 0, 1, dev, backend, a.steps, a.warmup, per_frame=True)
     if world > 1:
         dist.barrier()
-    r = run_sequence(a, W, H, tile, grid, rank, world, dev, backend, a.steps, a.warmup, per_frame=not a.sequence)
+    r = run_sequence(a, W, H, tile, grid, rank, world, dev, backend, a.steps, a.warmup, per_frame=not a.sequence,
+                     keep_output=a.dump_outputs is not None)
+    if a.dump_outputs is not None:  # what the timed path left after its last step
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "output.npy" if world == 1 else f"output_rank{rank}.npy"), r["output"])
     cfg = r["cfg"]
     # The metric's other resolutions (BASELINE.json: ms/frame @1080p & 4K, and
     # the 8K frame of the scaling target), single GPU only.
@@ -604,12 +699,12 @@ def main():
     # The same frames as one bmfr_process_sequence call per 64 frames (K2 of
     # frame f in K1 of f + 1's tail): the reference's own frame loop
     # (bmfr.cpp:417-485) enqueues every frame without waiting, as this does.
-    if world == 1 and not a.sequence and not a.no_sequence:
+    if world == 1 and a.full and not a.sequence and not a.no_sequence:
         rseq = run_sequence(a, W, H, (0, 0, W, H), None, 0, 1, dev, backend, a.steps, a.warmup, per_frame=False)
-    if world == 1 and not a.no_1080p and (W, H) != (1920, 1080):
+    if world == 1 and a.full and not a.no_1080p and (W, H) != (1920, 1080):
         r1080 = run_sequence(a, 1920, 1080, (0, 0, 1920, 1080), None, 0, 1, dev, backend, a.steps, a.warmup,
                              per_frame=not a.sequence)
-    if world == 1 and not a.no_8k and (W, H) != (7680, 4320):
+    if world == 1 and a.full and not a.no_8k and (W, H) != (7680, 4320):
         n8 = min(a.steps, a.frames_8k)
         r8k = run_sequence(a, 7680, 4320, (0, 0, 7680, 4320), None, 0, 1, dev, backend, n8, a.warmup,
                            per_frame=not a.sequence)
@@ -618,7 +713,7 @@ def main():
     # (fp16 feature buffers + 3rd-order features) and config 3 with f32
     # tmp_data, per-frame API, each with its own roofline.
     rvar = {}
-    if world == 1 and not a.no_variants and not a.sequence:
+    if world == 1 and a.full and not a.no_variants and not a.sequence:
         import copy
         other = ("exact", dict(third_order=False, input_half=False, half_tmp=1, fast_fit=False)) if a.fast_fit \
             else ("fast_fit", dict(third_order=False, input_half=False, half_tmp=1, fast_fit=True))
@@ -648,41 +743,45 @@ def main():
         ("_fastfit" if a.fast_fit else "")
     ms_per_frame = r["ms_per_frame"]
     if rank == 0:
-        achieved = k1_bytes_per_px(s) * tile_px / (r["k1_ms"] * 1e-3) / 1e9
-        k1_roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                   "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                   "kernel": "k_fused_cols (K1)" if a.half_tmp or a.fast_fit else "k_fused (K1)",
-                   "algorithmic_bytes_per_launch": k1_bytes_per_px(s) * tile_px}
-        if world == 1:
-            with_traffic(k1_roof, workload, r["k1_ms"])
-        if world == 1:
-            k1_roof.update(valu_roofline(a.fast_fit))
-        # Untiled per-frame runs below kTwoLaunchBlocks K1 blocks (bmfr_sizes
-        # frame_launches): the frame is one launch (K1 blocks + TAA tiles),
-        # the dominant -- only -- kernel of the timed region; its roofline is
-        # the frame's algorithmic bytes over its duration, and K1's own (timed
-        # apart, untimed pass) is roofline_k1.  Larger frames are two launches
-        # and K1, timed live by libbmfr's events, is the dominant kernel.
+        # A one-launch frame's kernels are timed by --full's untimed passes only:
+        # without them the line has no per-kernel times and no rooflines.
         one_launch = r["frame_kernel_ms"] is not None
-        if one_launch:
-            fb = frame_bytes_per_px(s) * tile_px
-            fa = fb / (r["frame_kernel_ms"] * 1e-3) / 1e9
-            roof = {"bound": "hbm", "achieved": round(fa, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(fa / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(workload + "_frame"),
-                    "kernel": ("k_fused_cols_taa<..., SAME = true>" if a.half_tmp or a.fast_fit
-                               else "k_fused_rows_taa<...>")
-                              + " (K1 + K2 of the frame, one launch)",
-                    "algorithmic_bytes_per_launch": fb, "launch_ms": round(r["frame_kernel_ms"], 4),
-                    "launch_ms_source": "HIP events around each frame's launch on its stream, in an untimed "
-                                        "pass over the same frames (the timed frames run without events between "
-                                        "them); the rocprofv3 kernel-trace mean of the same command is in "
-                                        "profiles/*_kernel_stats.md",
-                    "limiter": "K1 blocks: latency of phase-1 gathers and of the fit's pivot chain, VALU issue "
-                               "(roofline_k1); TAA tiles: texture path / latency (roofline_k2) -- not HBM"}
-        else:
-            roof = k1_roof
-        roof["frame_frac"] = round(frame_bytes_per_px(s) * W * H / (ms_per_frame * 1e-3) / 1e9 / (HBM_PEAK_GBS * world),
-                                   4)
+        roof = k1_roof = None
+        if r["k1_ms"] is not None:
+            achieved = k1_bytes_per_px(s) * tile_px / (r["k1_ms"] * 1e-3) / 1e9
+            k1_roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                       "kernel": "k_fused_cols (K1)" if a.half_tmp or a.fast_fit else "k_fused (K1)",
+                       "algorithmic_bytes_per_launch": k1_bytes_per_px(s) * tile_px}
+            if world == 1:
+                with_traffic(k1_roof, workload, r["k1_ms"])
+            if world == 1:
+                k1_roof.update(valu_roofline(a.fast_fit))
+            # Untiled per-frame runs below kTwoLaunchBlocks K1 blocks (bmfr_sizes
+            # frame_launches): the frame is one launch (K1 blocks + TAA tiles),
+            # the dominant -- only -- kernel of the timed region; its roofline is
+            # the frame's algorithmic bytes over its duration, and K1's own (timed
+            # apart, untimed pass) is roofline_k1.  Larger frames are two launches
+            # and K1, timed live by libbmfr's events, is the dominant kernel.
+            if one_launch:
+                fb = frame_bytes_per_px(s) * tile_px
+                fa = fb / (r["frame_kernel_ms"] * 1e-3) / 1e9
+                roof = {"bound": "hbm", "achieved": round(fa, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(fa / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(workload + "_frame"),
+                        "kernel": ("k_fused_cols_taa<..., SAME = true>" if a.half_tmp or a.fast_fit
+                                   else "k_fused_rows_taa<...>")
+                                  + " (K1 + K2 of the frame, one launch)",
+                        "algorithmic_bytes_per_launch": fb, "launch_ms": round(r["frame_kernel_ms"], 4),
+                        "launch_ms_source": "HIP events around each frame's launch on its stream, in an untimed "
+                                            "pass over the same frames (the timed frames run without events between "
+                                            "them); the rocprofv3 kernel-trace mean of the same command is in "
+                                            "profiles/*_kernel_stats.md",
+                        "limiter": "K1 blocks: latency of phase-1 gathers and of the fit's pivot chain, VALU issue "
+                                   "(roofline_k1); TAA tiles: texture path / latency (roofline_k2) -- not HBM"}
+            else:
+                roof = k1_roof
+            roof["frame_frac"] = round(frame_bytes_per_px(s) * W * H / (ms_per_frame * 1e-3) / 1e9
+                                       / (HBM_PEAK_GBS * world), 4)
         line = {
             "metric": "ms/frame @1080p & 4K, 1/2/4/8 GPU; PSNR vs 4096spp reference",
             "value": round(ms_per_frame, 4),
@@ -714,13 +813,16 @@ def main():
                                        f"{' overlapped with interior blocks' if a.overlap else ''}")
                        if world > 1 else "single GPU"},
             "device_ms_per_frame": round(r["dev_ms"], 4),
-            "kernel_ms": {"fused_block_k1": round(r["k1_ms"], 4), "taa_k2": round(r["k2_ms"], 4)},
-            "psnr_db": {"output": round(r["psnr"], 2), "noisy_input": round(r["psnr_in"], 2)},
-            "roofline": roof,
         }
+        if r["k1_ms"] is not None:
+            line["kernel_ms"] = {"fused_block_k1": round(r["k1_ms"], 4), "taa_k2": round(r["k2_ms"], 4)}
+        if r["psnr"] is not None:
+            line["psnr_db"] = {"output": round(r["psnr"], 2), "noisy_input": round(r["psnr_in"], 2)}
+        if roof is not None:
+            line["roofline"] = roof
         if one_launch:
             line["roofline_k1"] = k1_roof
-        if world == 1:
+        if world == 1 and r["k2_ms"] is not None:
             k2 = k2_bytes_per_px(s) * tile_px / (r["k2_ms"] * 1e-3) / 1e9 if not a.sequence else None
             if k2:
                 line["roofline_k2"] = with_traffic(
@@ -755,7 +857,7 @@ def main():
             line[f"ms_per_frame_{key}"] = variant_line(rv, vs, W, H, wl, "k_fused_cols_taa<..., SAME = true>"
                                                        if b.half_tmp or b.fast_fit else "k_fused_rows_taa<...>",
                                                        "k_fused_cols" if b.half_tmp or b.fast_fit else "k_fused")
-        if world == 1 and a.cpu_frames > 0:
+        if world == 1 and a.full and a.cpu_frames > 0:
             line["cpu_baseline"] = cpu_baseline(cfg, a.cpu_frames, a.seed)
         print(json.dumps(line), flush=True)
     if world > 1:
