@@ -482,10 +482,7 @@ __device__ __forceinline__ void k1_rows_body(const Params& P, const K1Args& A, K
 
 // Minimum waves per SIMD for the register allocator at B = 13: four (128
 // VGPRs, 12-32 bytes of spills) instead of three (129-130 VGPRs).
-#ifndef BMFR_ROWS_MIN_WAVES
-#define BMFR_ROWS_MIN_WAVES 4
-#endif
-constexpr int kRowsMinWaves = BMFR_ROWS_MIN_WAVES;
+constexpr int kRowsMinWaves = 4;
 template <int NS, int FS, class IN, bool FAST = false>
 __global__ __launch_bounds__(kThreads, FS == 6 ? kRowsMinWaves : 3) void k_fused(Params P, K1Args A) {
     __shared__ K1Lds<NS + FS + 3> L;
@@ -495,15 +492,16 @@ __global__ __launch_bounds__(kThreads, FS == 6 ? kRowsMinWaves : 3) void k_fused
 // The one-launch frame with this K1 (f32 tmp_data): K1 blocks, then the
 // frame's TAA tiles waiting on their completion flags (as k_fused_cols_taa,
 // bmfr_fused_cols.hip).
+static_assert(kThreads == kTileThreads, "the TAA tiles run on this kernel's work-groups");
 template <int NS, int FS, class IN, bool FAST = false>
 __global__ __launch_bounds__(kThreads, FS == 6 ? kRowsMinWaves : 3) void k_fused_rows_taa(Params P, K1Args A, TaaArgs T, int nk1, int nk1p) {
     __shared__ union {
         K1Lds<NS + FS + 3> k1;
-        FrameTaaLds<kThreads> k2;
+        FrameTaaLds k2;
     } U;
     const int b = blockIdx.x;
     if (b < nk1) k1_rows_body<NS, FS, IN, true, FAST>(P, A, U.k1, xcd_swizzle(b, nk1));
-    else if (b >= nk1p) frame_taa_part<IN, true, kThreads>(P, T, b, nk1p, U.k2);
+    else if (b >= nk1p) frame_taa_part<IN, true>(P, T, b, nk1p, U.k2);
 }
 
 bool fused_supported(const Params& P) {
@@ -537,7 +535,7 @@ template <int FS, class IN, bool FAST>
 struct LaunchRowsFrame {
     static void go(const Params& P, hipStream_t st, const FusedArgs& A) {
         const int nk1 = P.ring < 0 || P.nbx <= 0 || P.nby <= 0 ? 0 : k1_blocks(P), nk1p = (nk1 + 7) & ~7;
-        hipLaunchKernelGGL((k_fused_rows_taa<4, FS, IN, FAST>), dim3(nk1p + frame_taa_tiles<kThreads>(P)),
+        hipLaunchKernelGGL((k_fused_rows_taa<4, FS, IN, FAST>), dim3(nk1p + frame_taa_tiles(P)),
                            dim3(kThreads), 0, st, P, k1_args(A), taa_args(A), nk1, nk1p);
     }
 };

@@ -36,15 +36,21 @@
 namespace bmfr {
 namespace cols {
 
-// Waves per work-group NW = 4 (the default) or 8: 64 NW threads; in phase 1
-// and 3 a thread owns kItems = 16 / NW rows of the block.
-template <int NW>
-constexpr int threads_of() { return 64 * NW; }
-template <int NW>
-constexpr int items_of() { return 16 / NW; }
+// Four waves per work-group (256 threads): in phases 1 and 3 a thread owns
+// kItems = 4 rows of the block, in the fit a wave owns every fourth column.
+// (Eight waves -- half the rows per thread, fewer columns per wave, three
+// work-groups of 80 VGPRs per CU -- lost by 34 % in round 3.)
+constexpr int kNW = 4;
+constexpr int kK1Threads = 64 * kNW;
+static_assert(kK1Threads == kTileThreads, "the frame kernels' TAA tiles run on K1's work-groups");
+constexpr int kItems = 16 / kNW;
 constexpr int kSlots = 16;    // rows per lane per column (row = lane + 64 j)
 constexpr int kUStride = 20;     // floats per lane in a u buffer: 16 + 4 (conflict-free 16-byte reads)
-constexpr int kPre = 2;          // step-0 noise columns per wave prefetched in phase 1
+// Step-0 noise columns per wave prefetched in phase 1 (slots whose column is a
+// feature column for every wave).  B = 16 as well since round 6 (its K1 now
+// has the registers: 108 VGPRs with them, no spills; config 5's K1 -1.7 to
+// -2.2 % against none, profiles/r06_ab_np16.txt).
+constexpr int kPre = 2;
 
 // Householder vectors in flight: the fit's waves wait for each published
 // pivot through an LDS flag instead of a barrier per column, so a buffer is
@@ -55,7 +61,7 @@ constexpr int kUBufs = 3;
 // buffers (B >= 16) they wait in registers until the fit has loaded its
 // columns and then go there, so the work-group's LDS stays within 40 KB (four
 // work-groups per CU); otherwise they have their own LDS array.
-constexpr int kKeep = 16 * 3 * 64;  // 12 floats per thread at NW = 4, 6 at NW = 8
+constexpr int kKeep = 16 * 3 * 64;  // 12 floats per thread
 // F32: f32 tmp_data (USE_HALF_PRECISION_IN_TMP_DATA 0): the design matrix as
 // floats -- twice the registers per column (16 per lane, as 8 float pairs),
 // the trailing columns never rounded to half.  Only the rows another wave
@@ -77,7 +83,7 @@ struct FitOut {
     float weights[(B - 3) * 3];
     float mm[3 * (B - 3)];
 };
-template <int B, int NW = 4, bool F32 = false>
+template <int B, bool F32 = false>
 struct Lds {
     using MT = std::conditional_t<F32, float, _Float16>;
     static constexpr int kMBytes = (B - 1) * 64 * m_slots<F32>() * (F32 ? 4 : 2);
@@ -102,10 +108,10 @@ struct Lds {
         else return fo_own[0];
     }
     float keep_s[keep_in_m(B, F32) ? 1 : kKeep];
-    __device__ float* keep() { return keep_in_m(B, F32) ? keep_m : keep_s; }  // [(item * 3 + ch) * 64 NW + t]
+    __device__ float* keep() { return keep_in_m(B, F32) ? keep_m : keep_s; }  // [(item * 3 + ch) * 256 + t]
     float piv[kUBufs][3];               // |u|^2 and RN(1/|u|^2) (fast_fit: 2 RN(1/|u|^2)) of the published vector; fast_fit: u's pivot element
     int pub;                            // highest published pivot column
-    int prog[NW];                       // per wave: the last step it has applied
+    int prog[kNW];                      // per wave: the last step it has applied
     int timeout;                        // a flag wait of this block gave up (reported once, at the end)
     int max_polls;                      // Params::max_polls (kept here: read only once a flag is not ready)
     int delay;                          // Params::debug_delay (diagnostics, read at the block's end)
@@ -130,10 +136,8 @@ template <bool F32>
 using Pair = std::conditional_t<F32, f2v, h2>;
 template <class P2>
 __device__ __forceinline__ float hget(const P2 (&a)[8], int j) { return (float)a[j >> 1][j & 1]; }
-template <class P2>
-__device__ __forceinline__ void hset(P2 (&a)[8], int j, float v) {
-    if constexpr (std::is_same_v<P2, h2>) a[j >> 1][j & 1] = (_Float16)v;  // vstore_half, round to nearest even
-    else a[j >> 1][j & 1] = v;
+__device__ __forceinline__ void hset(h2 (&a)[8], int j, float v) {
+    a[j >> 1][j & 1] = (_Float16)v;  // vstore_half, round to nearest even
 }
 
 __device__ __forceinline__ float lane_value(float v, int lane) {
@@ -143,12 +147,6 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
 // Phase 1 -> 3 in registers: an item's normal and position as loaded.  f32
 // inputs: six floats.  Half inputs: the 12 bytes in three registers (the two
 // .xy words and both .z halves in one), not four.
-#ifndef BMFR_KEEP_NP_HALF_IN
-#define BMFR_KEEP_NP_HALF_IN 0
-#endif
-#ifndef BMFR_KEEP_NP_F32
-#define BMFR_KEEP_NP_F32 0
-#endif
 template <class IN>
 struct KeptNP {
     In3<IN> n, p;
@@ -321,76 +319,29 @@ __device__ __forceinline__ void update_column(h2 (&a)[8], const float (&u)[kSlot
     __builtin_amdgcn_sched_barrier(0);  // one column in flight: bounds the register footprint
 }
 
-// f32 tmp_data (F32): the column update of step c >= 1 on float pairs.  The
-// dot's four partial chains are upstream's sums of rounded products
-// (bmfr.cl:608-617: tmp * u_vec, then +=) -- chains (0, 1) and (2, 3) as
-// packed pairs, every lane rounding as the scalar ops --, reduced in
-// upstream's association; then the update of bmfr.cl:646 as in
-// update_column (packed Markstein quotients, rows above the pivot kept).
-// FAST (fast_fit): fused dot chains, the butterfly sum, and one fused
-// multiply-add per element on RN(c2 / |u|^2).
-template <int c, bool FAST>
-__device__ __forceinline__ void update_column_f32(f2v (&a)[8], const float (&u)[kSlots], float ulen2, float recip,
-                                                  int l) {
+// f32 tmp_data (F32, fast_fit only): the column update of step c >= 1 on
+// float pairs.  The dot's four partial chains -- chains (0, 1) and (2, 3) as
+// packed pairs -- are fused, summed by the butterfly; then one fused
+// multiply-add per element on RN(c2 / |u|^2), rows above the pivot kept.
+// recip = 2 RN(1/|u|^2) (publish_pivot).
+template <int c>
+__device__ __forceinline__ void update_column_f32(f2v (&a)[8], const float (&u)[kSlots], float recip, int l) {
     f2v p01 = {0.f, 0.f}, p23 = {0.f, 0.f};
 #pragma unroll
     for (int si = 0; si < 4; ++si) {
         const f2v u01 = {u[4 * si], u[4 * si + 1]}, u23 = {u[4 * si + 2], u[4 * si + 3]};
-        if constexpr (FAST) {  // fused
-            p01 = __builtin_elementwise_fma(a[2 * si], u01, p01);
-            p23 = __builtin_elementwise_fma(a[2 * si + 1], u23, p23);
-        } else {
-            p01 = p01 + a[2 * si] * u01;
-            p23 = p23 + a[2 * si + 1] * u23;
-        }
+        p01 = __builtin_elementwise_fma(a[2 * si], u01, p01);
+        p23 = __builtin_elementwise_fma(a[2 * si + 1], u23, p23);
         if (si == 0) p01.x = l >= c ? p01.x : 0.f;  // rows above the pivot: skipped
     }
     const float p[4] = {p01.x, p01.y, p23.x, p23.y};
-    if constexpr (FAST) {  // recip = 2 RN(1/|u|^2) (publish_pivot)
-        const float sc = wave_reduce_fast<RedOp::Sum>(p) * recip;
-        const f2v vs = {sc, sc};
-        const float keep0 = a[0].x;
+    const float sc = wave_reduce_fast<RedOp::Sum>(p) * recip;
+    const f2v vs = {sc, sc};
+    const float keep0 = a[0].x;
 #pragma unroll
-        for (int k = 0; k < kSlots / 2; ++k)
-            a[k] = __builtin_elementwise_fma(-f2v{u[2 * k], u[2 * k + 1]}, vs, a[k]);
-        a[0].x = l >= c ? a[0].x : keep0;  // rows above the pivot keep their value
-        __builtin_amdgcn_sched_barrier(0);
-        return;
-    }
-    const float c2 = 2.f * wave_reduce<RedOp::Sum>(p);
-    f2v q[kSlots / 2];
-    if (fabsf(c2) < 0x1p100f && ulen2 >= 0x1p-100f && ulen2 < 0x1p100f) {
-        const f2v vb = {ulen2, ulen2}, vy = {recip, recip};
-#pragma unroll
-        for (int k = 0; k < kSlots / 2; ++k) {
-            const f2v av = f2v{u[2 * k], u[2 * k + 1]} * c2;
-            const f2v q0 = av * vy;
-            const f2v r = __builtin_elementwise_fma(-q0, vb, av);
-            q[k] = __builtin_elementwise_fma(r, vy, q0);
-        }
-    } else {
-        // Cold (never taken on finite data): IEEE division in a rolled loop
-        // rotating u and q by one pair (as update_column: no indexed arrays)
-        float uu[kSlots];
-#pragma unroll
-        for (int j = 0; j < kSlots; ++j) uu[j] = u[j];
-#pragma unroll 1
-        for (int k = 0; k < kSlots / 2; ++k) {
-            const f2v qk = {(uu[0] * c2) / ulen2, (uu[1] * c2) / ulen2};
-            const float u0 = uu[0], u1 = uu[1];
-#pragma unroll
-            for (int j = 0; j < kSlots - 2; ++j) uu[j] = uu[j + 2];
-            uu[kSlots - 2] = u0;
-            uu[kSlots - 1] = u1;
-#pragma unroll
-            for (int i = 0; i < kSlots / 2 - 1; ++i) q[i] = q[i + 1];
-            q[kSlots / 2 - 1] = qk;
-        }
-    }
-    q[0].x = l >= c ? q[0].x : 0.f;  // x - (+0) == x: rows above the pivot keep their value
-#pragma unroll
-    for (int k = 0; k < kSlots / 2; ++k) a[k] = a[k] - q[k];
-    __builtin_amdgcn_sched_barrier(0);  // one column in flight: bounds the register footprint
+    for (int k = 0; k < kSlots / 2; ++k) a[k] = __builtin_elementwise_fma(-f2v{u[2 * k], u[2 * k + 1]}, vs, a[k]);
+    a[0].x = l >= c ? a[0].x : keep0;  // rows above the pivot keep their value
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // Step 0: column 0 is FEATURE_BUFFERS[0] = 1.f, so u = (1 - 32, 1, 1, ...),
@@ -404,6 +355,7 @@ __device__ __forceinline__ void update_column_f32(f2v (&a)[8], const float (&u)[
 template <bool FAST = false, class P2>
 __device__ __forceinline__ void update_column0(P2 (&a)[8], int l, const float* __restrict__ noise,
                                                const float (&pre)[kSlots], bool use_pre, double noise2) {
+    static_assert(FAST || std::is_same_v<P2, h2>, "f32 tmp_data: the fast fit only");
     float x[kSlots];
 #pragma unroll
     for (int j = 0; j < kSlots; ++j) x[j] = hget(a, j);
@@ -453,37 +405,36 @@ __device__ __forceinline__ void update_column0(P2 (&a)[8], int l, const float* _
 #pragma unroll
             for (int k = 0; k < 8; ++k) a[k] = xp[k];
         }
-        __builtin_amdgcn_sched_barrier(0);
-        return;
-    }
-    float p[4];
+    } else {  // the exact fit: half tmp_data only
+        float p[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        float s = 0.f;
+        for (int m = 0; m < 4; ++m) {
+            float s = 0.f;
 #pragma unroll
-        for (int si = 0; si < 4; ++si) {
-            const int j = m + 4 * si;
-            s = s + (j == 0 && l == 0 ? x[0] * -31.f : x[j]);
+            for (int si = 0; si < 4; ++si) {
+                const int j = m + 4 * si;
+                s = s + (j == 0 && l == 0 ? x[0] * -31.f : x[j]);
+            }
+            p[m] = s;
         }
-        p[m] = s;
-    }
-    const float c2 = 2.f * wave_reduce<RedOp::Sum>(p);
-    constexpr float ulen2 = 1984.f;
-    const float recip = 1.f / ulen2;
-    float q, q0;
-    if (fabsf(c2) < 0x1p100f) {
-        q = div_by_recip(c2, ulen2, recip);
-        q0 = div_by_recip(-31.f * c2, ulen2, recip);
-    } else {
-        q = c2 / ulen2;
-        q0 = (-31.f * c2) / ulen2;
-    }
-    float nv[kSlots];
+        const float c2 = 2.f * wave_reduce<RedOp::Sum>(p);
+        constexpr float ulen2 = 1984.f;
+        const float recip = 1.f / ulen2;
+        float q, q0;
+        if (fabsf(c2) < 0x1p100f) {
+            q = div_by_recip(c2, ulen2, recip);
+            q0 = div_by_recip(-31.f * c2, ulen2, recip);
+        } else {
+            q = c2 / ulen2;
+            q0 = (-31.f * c2) / ulen2;
+        }
+        float nv[kSlots];
 #pragma unroll
-    for (int j = 0; j < kSlots; ++j) nv[j] = x[j] - q;
-    nv[0] = l == 0 ? x[0] - q0 : nv[0];
+        for (int j = 0; j < kSlots; ++j) nv[j] = x[j] - q;
+        nv[0] = l == 0 ? x[0] - q0 : nv[0];
 #pragma unroll
-    for (int j = 0; j < kSlots; ++j) hset(a, j, nv[j]);
+        for (int j = 0; j < kSlots; ++j) hset(a, j, nv[j]);
+    }
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -511,9 +462,9 @@ template <class LDS>
 __device__ __forceinline__ void wait_pub(LDS& L, int c) {
     wait_flag(L, &L.pub, c);
 }
-template <int NW, class LDS>
+template <class LDS>
 __device__ __forceinline__ void wait_all_progress(LDS& L, int c) {
-    for (int w = 0; w < NW; ++w) wait_flag(L, &L.prog[w], c);
+    for (int w = 0; w < kNW; ++w) wait_flag(L, &L.prog[w], c);
 }
 
 // The owner of pivot column c (>= 1), once steps 0..c-1 are applied to it:
@@ -521,17 +472,18 @@ __device__ __forceinline__ void wait_all_progress(LDS& L, int c) {
 // published to LDS with the R column.  FAST (fast_fit): hardware sqrt /
 // reciprocal, butterfly sum, fused squares; with half tmp_data u published
 // as the column's halves (HALVES), with f32 tmp_data as floats.
-template <int c, int B, int NW, bool FAST = false, class P2, class LDS>
+template <int c, int B, bool FAST = false, class P2, class LDS>
 __device__ __forceinline__ void publish_pivot(const P2 (&a)[8], LDS& L, int l) {
     constexpr int RE = B - 2;
     constexpr bool F32 = std::is_same_v<P2, f2v>;
+    static_assert(!F32 || FAST, "f32 tmp_data: the fast fit only");
     constexpr bool HALVES = FAST && !F32;
     float x[kSlots];
 #pragma unroll
     for (int j = 0; j < kSlots; ++j) x[j] = hget(a, j);
     // |x|^2 over rows >= c + 1 (bmfr.cl:555-569): squares of halves are
     // exact, so the fused square-and-add chains are upstream's sums bit for
-    // bit; f32 squares are rounded, then added (upstream's strict sequence).
+    // bit (f32 squares, fast_fit only, lose upstream's rounding of the square).
     float p[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -540,8 +492,7 @@ __device__ __forceinline__ void publish_pivot(const P2 (&a)[8], LDS& L, int l) {
         for (int si = 0; si < 4; ++si) {
             const int j = m + 4 * si;
             const float xj = j == 0 && l < c + 1 ? 0.f : x[j];
-            if constexpr (F32 && !FAST) s = s + xj * xj;
-            else s = __builtin_fmaf(xj, xj, s);
+            s = __builtin_fmaf(xj, xj, s);
         }
         p[m] = s;
     }
@@ -554,7 +505,7 @@ __device__ __forceinline__ void publish_pivot(const P2 (&a)[8], LDS& L, int l) {
     const float ulen2 = sumsq + ucl2 * ucl2;
     if (l == c) x[0] = ucl2;
     constexpr int buf = c % kUBufs;
-    if constexpr (c >= kUBufs) wait_all_progress<NW>(L, c - kUBufs);  // readers of u_{c-3} done
+    if constexpr (c >= kUBufs) wait_all_progress(L, c - kUBufs);  // readers of u_{c-3} done
     if constexpr (HALVES) {  // u as the column's halves, rows <= c zeroed; the pivot element in piv[2]
         uint32_t w[8];
 #pragma unroll
@@ -592,12 +543,13 @@ __device__ __forceinline__ void publish_pivot(const P2 (&a)[8], LDS& L, int l) {
 // wait for its global loads and stores (__syncthreads() does).
 __device__ __forceinline__ void k1_barrier() { lds_barrier(); }
 
-// Wave W's part of the fit: columns c = 1 + W + NW k (slot k); column 0 is
-// implicit.  W is a run-time (wave-uniform) value, so the NW waves run one
+// Wave W's part of the fit: columns c = 1 + W + kNW k (slot k); column 0 is
+// implicit.  W is a run-time (wave-uniform) value, so the four waves run one
 // copy of the code: column ownership is a scalar branch, while the slot of
 // every column a step touches is known at compile time.
-template <int NS, int FS, int NW = 4, bool FAST = false, bool F32 = false>
+template <int NS, int FS, bool FAST = false, bool F32 = false>
 struct WaveFit {
+    static_assert(!F32 || FAST, "f32 tmp_data: the fast fit only (the exact f32 fit is bmfr_fused.hip's)");
     static constexpr int B = NS + FS + 3;
     // fast_fit (FAST): the fused trailing update, butterfly reductions, f32
     // noise add, hardware sqrt / reciprocals, scaling by the reciprocal; with
@@ -606,23 +558,13 @@ struct WaveFit {
     static constexpr bool FASTR = FAST && !F32;
     using P2 = Pair<F32>;
     static constexpr int NF = B - 3;  // pivot columns
-    static constexpr int NSL = (B - 1 + NW - 1) / NW;
-    static constexpr int NT = 64 * NW, NI = 16 / NW;  // threads, items (rows) per thread in phases 1 and 3
-    using LDS = Lds<B, NW, F32>;
-    static __device__ __forceinline__ bool owns(int W, int c) { return c >= 1 && c < B && (c - 1) % NW == W; }
-    static constexpr int owner(int c) { return (c - 1) % NW; }
-    static constexpr int slot(int c) { return (c - 1) / NW; }
-    // Step-0 noise columns prefetched per wave (slots whose column is a
-    // feature column for every wave), loaded in phase 1.  B = 16 with four
-    // waves: two as well since round 6 (its K1 now has the registers: 108
-    // VGPRs with them, no spills; config 5's K1 -1.7 to -2.2 %,
-    // profiles/r06_ab_np16.txt); -DBMFR_NP16=0 gives none.
-#ifndef BMFR_NP16
-#define BMFR_NP16 2
-#endif
-    static constexpr int NP = B >= 16 && NW == 4 ? BMFR_NP16 : ((NF - 1) / NW < kPre ? (NF - 1) / NW : kPre);
-    static_assert(!F32 || NW == 4, "f32 tmp_data: row quad w of wave w");
-    static_assert(NP == 0 || NW * NP < NF, "prefetched slots hold feature columns");
+    static constexpr int NSL = (B - 1 + kNW - 1) / kNW;
+    using LDS = Lds<B, F32>;
+    static __device__ __forceinline__ bool owns(int W, int c) { return c >= 1 && c < B && (c - 1) % kNW == W; }
+    static constexpr int owner(int c) { return (c - 1) % kNW; }
+    static constexpr int slot(int c) { return (c - 1) / kNW; }
+    // the wave's first kPre slots (prefetched step-0 noise) hold feature columns
+    static_assert(kNW * kPre < NF, "prefetched slots hold feature columns");
 
     // The first column a wave updates at step 0: a feature column for every wave.
     static __device__ __forceinline__ int first_column(int W) { return 1 + W; }
@@ -635,18 +577,18 @@ struct WaveFit {
         const bool publish = nxt < NF && W == owner(nxt);
         if constexpr (c == 0) {
             if (publish) {  // column 1 of wave 0: its first column
-                update_column0<FAST>(a[slot(nxt)], l, noise + (nxt - 1) * kBlockPixels, pre[0], NP > 0, noise2);
-                publish_pivot<nxt, B, NW, FAST>(a[slot(nxt)], L, l);
+                update_column0<FAST>(a[slot(nxt)], l, noise + (nxt - 1) * kBlockPixels, pre[0], true, noise2);
+                publish_pivot<nxt, B, FAST>(a[slot(nxt)], L, l);
             }
             sfor<NSL>([&](auto K) {
                 constexpr int k = decltype(K)::value;
-                const int fb = 1 + W + NW * k;
-                if (owns(W, fb) && !(publish && fb == nxt))  // slots < NP: feature columns, prefetched
+                const int fb = 1 + W + kNW * k;
+                if (owns(W, fb) && !(publish && fb == nxt))  // slots < kPre: feature columns, prefetched
                     update_column0<FAST>(a[k], l, fb < NF ? noise + (fb - 1) * kBlockPixels : nullptr,
-                                   pre[k < kPre ? k : 0], k < NP, noise2);
+                                   pre[k < kPre ? k : 0], k < kPre, noise2);
             });
         } else {
-            if (1 + W + NW * ((B - 2 - W) / NW) > c) {  // this wave's last column is past the pivot
+            if (1 + W + kNW * ((B - 2 - W) / kNW) > c) {  // this wave's last column is past the pivot
                 wait_pub(L, c);
                 float u[FASTR ? 1 : kSlots];
                 h2 uh[FASTR ? 8 : 1];
@@ -671,20 +613,20 @@ struct WaveFit {
                 }
                 const float ulen2 = L.piv[c % kUBufs][0], recip = L.piv[c % kUBufs][1];
                 auto upd = [&](P2 (&col)[8]) {
-                    if constexpr (F32) update_column_f32<c, FAST>(col, u, ulen2, recip, l);
+                    if constexpr (F32) update_column_f32<c>(col, u, recip, l);
                     else if constexpr (FAST) update_column_fast<c>(col, uh, uc, recip);
                     else update_column<c>(col, u, ulen2, recip, l);
                 };
                 if constexpr (nxt < NF) {
                     if (publish) {  // the next pivot is every wave's critical path: issue it first
                         upd(a[slot(nxt)]);
-                        publish_pivot<nxt, B, NW, FAST>(a[slot(nxt)], L, l);
+                        publish_pivot<nxt, B, FAST>(a[slot(nxt)], L, l);
                     }
                 }
                 sfor<NSL>([&](auto K) {
                     constexpr int k = decltype(K)::value;
-                    const int fb = 1 + W + NW * k;
-                    if constexpr (NW * k + NW > c) {  // slot k holds columns <= NW k + NW
+                    const int fb = 1 + W + kNW * k;
+                    if constexpr (kNW * k + kNW > c) {  // slot k holds columns <= 4 k + 4
                         if (owns(W, fb) && fb > c && !(publish && fb == nxt)) upd(a[k]);
                     }
                 });
@@ -701,15 +643,15 @@ struct WaveFit {
         (step<C>(a, L, W, l, noise, pre, noise2), ...);
     }
 
-    // Step 0's noise for the wave's first NP columns (1 + W, 1 + W + NW:
+    // Step 0's noise for the wave's first kPre columns (1 + W, 1 + W + kNW:
     // feature columns for every wave), loaded while the last items of phase 1
     // finish (the fit's first dependent loads); the other noisy columns load
     // in step 0.
     static __device__ __forceinline__ void prefetch_noise(int W, int l, const float* __restrict__ noise,
                                                           float (&pre)[kPre][kSlots]) {
 #pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const float* src = noise + (first_column(W) + NW * k - 1) * kBlockPixels + l;
+        for (int k = 0; k < kPre; ++k) {
+            const float* src = noise + (first_column(W) + kNW * k - 1) * kBlockPixels + l;
 #pragma unroll
             for (int j = 0; j < kSlots; ++j) pre[k][j] = src[64 * j];
         }
@@ -717,11 +659,11 @@ struct WaveFit {
 
     static __device__ __forceinline__ void run(LDS& L, int W, int l, const float* __restrict__ noise,
                                                const float (&pre)[kPre][kSlots], double noise2, int mp,
-                                               const float (&kp)[NI][3], const f2v (&own)[NSL][2]) {
+                                               const float (&kp)[kItems][3], const f2v (&own)[NSL][2]) {
         P2 a[NSL][8];
         sfor<NSL>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            const int c = 1 + W + NW * k;
+            const int c = 1 + W + kNW * k;
             if (owns(W, c)) {
                 if constexpr (F32) {
                     // quad W from phase 1's registers, the others from LDS (a lane
@@ -747,25 +689,25 @@ struct WaveFit {
                 }
             }
         });
-        if (W == 0 && l < NW + 3) {  // read only after the barrier below
+        if (W == 0 && l < kNW + 3) {  // read only after the barrier below
             if (l == 0) L.pub = 0;
-            else if (l == NW + 1) L.timeout = 0;
-            else if (l == NW + 2) L.max_polls = mp;
+            else if (l == kNW + 1) L.timeout = 0;
+            else if (l == kNW + 2) L.max_polls = mp;
             else L.prog[l - 1] = -1;
         }
         k1_barrier();  // the u buffers alias M
         if constexpr (keep_in_m(B, F32)) {  // phase 1's kept colours into the matrix area beside the u buffers
             const int t = W * 64 + l;
 #pragma unroll
-            for (int i = 0; i < NI; ++i)
+            for (int i = 0; i < kItems; ++i)
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) L.keep_m[(i * 3 + ch) * NT + t] = kp[i][ch];
+                for (int ch = 0; ch < 3; ++ch) L.keep_m[(i * 3 + ch) * kK1Threads + t] = kp[i][ch];
         }
 
         // Scale the position features to the block's [min, max] (bmfr.cl:510-542).
         sfor<NSL>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            const int c = 1 + W + NW * k;
+            const int c = 1 + W + kNW * k;
             if (owns(W, c) && c >= NS && c < NF) {
                 float bmax, bmin;
                 if constexpr (FASTR) {  // min / max of the packed halves (NaN-free: phase 1 maps NaN to 0)
@@ -826,14 +768,12 @@ struct WaveFit {
         });
         if (W == 0 && l < 3) L.fo().R[l] = 32.f;  // R(0,0) = |column 0|
 
-#ifndef BMFR_PROBE_K1_NOQR  // timing probe (wrong results): no Householder steps
         steps(a, L, W, l, noise, pre, noise2, std::make_integer_sequence<int, NF>{});
-#endif
 
         // Right-hand side: rows 0..B-4 of the colour columns (bmfr.cl:596-600).
         sfor<NSL>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            const int c = 1 + W + NW * k;
+            const int c = 1 + W + kNW * k;
             if (owns(W, c) && c >= NF) {
                 if (l < NF) L.fo().R[((B - 3) * (B - 2) + l) * 3 + (c - NF)] = hget(a[k], 0);
             }
@@ -861,9 +801,6 @@ __device__ __forceinline__ float row_bcast(float v) {  // every lane <- lane N o
 }
 // FAST (fast_fit): the division by the diagonal as a multiply by the
 // hardware reciprocal (1 ulp), which shortens the step chain's latency.
-#ifndef BMFR_FAST_BACKSUB
-#define BMFR_FAST_BACKSUB 1
-#endif
 template <int B, bool FAST, class LDS>
 __device__ __forceinline__ void back_substitute_regs(LDS& L, int t) {
     constexpr int RE = B - 2;
@@ -877,7 +814,7 @@ __device__ __forceinline__ void back_substitute_regs(LDS& L, int t) {
     sfor<RE - 1>([&](auto I) {
         constexpr int i = RE - 2 - decltype(I)::value;
         const float div = row_bcast<i>(col[i]);
-        if constexpr (FAST && BMFR_FAST_BACKSUB) {
+        if constexpr (FAST) {
             const float r = __builtin_amdgcn_rcpf(div);
             if (live && x >= i) col[i] = col[i] * r;
         } else {
@@ -914,12 +851,13 @@ __device__ __forceinline__ void back_substitute_regs(LDS& L, int t) {
 // COH: the TAA tiles of the same frame run in this launch: the accumulated
 // colour and the reprojected positions they read are stored device-coherent
 // and the block publishes done[g] = epoch once they are.
-template <int NS, int FS, class IN, bool COH = false, int NW = 4, bool FAST = false, bool F32 = false>
-__device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, Lds<NS + FS + 3, NW, F32>& L, int g) {
+template <int NS, int FS, class IN, bool COH = false, bool FAST = false, bool F32 = false>
+__device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, Lds<NS + FS + 3, F32>& L, int g) {
     constexpr int B = NS + FS + 3;
     constexpr bool FASTR = FAST && !F32;  // WaveFit::FASTR
     using P2 = Pair<F32>;
-    constexpr int NT = 64 * NW, NI = 16 / NW;  // threads; items (rows) per thread
+    using Fit = WaveFit<NS, FS, FAST, F32>;
+    constexpr int NT = kK1Threads, NI = kItems;  // threads; items (rows) per thread
     const int t = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     const int l = t & 63;
@@ -942,22 +880,17 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
     if constexpr (COH)
         if (t == 0) L.flag = (by - P.by0) * P.nbx + (bx - P.bx0);
     // Item i of wave w: block row pair 2 (NI w + i) (a wave sweeps its own 8
-    // rows), or with kInterleave 2 (NW i + w) (the work-group's waves sweep
+    // rows), or with kInterleave 2 (kNW i + w) (the work-group's waves sweep
     // the block together, neighbouring row pairs at a time: their previous-
     // frame taps share cache lines); lanes 0-31 / 32-63 take the pair's rows.
     // The design-matrix row of a pixel (its index in the block) is the same
     // either way: only which thread computes it changes.
     // kInterleave with fast_fit: K1 -1.1 %; on the exact path +1.1 % (its
-    // half-at-a-time matrix stores), so not there (profiles/r04_ab_row_interleave.txt).
-#ifndef BMFR_K1_INTERLEAVE
-#define BMFR_K1_INTERLEAVE (FASTR ? 1 : 0)
-#endif
-    // 0: own 8 rows; 1: slot NW i + w; 2: item pairs interleaved (slots 2 NW (i / 2) + 2 w + (i & 1):
-    // a thread's two items of a pair stay adjacent slots, one 4-byte store per column)
-    constexpr int kIlv = F32 ? 0 : BMFR_K1_INTERLEAVE;  // f32: wave w computes row quad w (compacted matrix)
-    constexpr bool kInterleave = kIlv == 1;
+    // half-at-a-time matrix stores), so not there (profiles/r04_ab_row_interleave.txt);
+    // f32 tmp_data: wave w computes row quad w (compacted matrix).
+    constexpr bool kInterleave = FASTR;
     auto item_slot = [&](int i) {  // row slot j: rows l + 64 j
-        return kIlv == 1 ? NW * i + w : (kIlv == 2 ? 2 * NW * (i / 2) + 2 * w + (i & 1) : NI * w + i);
+        return kInterleave ? kNW * i + w : NI * w + i;
     };
     const int lx = l & (kEdge - 1);
     auto item_row = [&](int lane, int i) { return (lane >> 5) + 2 * item_slot(i); };
@@ -965,8 +898,8 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
     // ---- accumulate_noisy_data (bmfr.cl:310-484), rows l + 64 (NI w + i) ----
     P2 pk[B];            // features of an item pair, packed for one LDS store per column
     // F32: this wave's row quad of the columns it owns in the fit (slot k:
-    // column 1 + w + NW k), never stored to LDS
-    f2v own[WaveFit<NS, FS, NW, FAST, F32>::NSL][2];
+    // column 1 + w + kNW k), never stored to LDS
+    f2v own[Fit::NSL][2];
     uint32_t spps = 0;   // per item i, bits 8i..8i+7: its new spp
     uint32_t ibits = 0;  // per item i, bit i: owner; bit 4 + i: accepted taps with weight > 0
     int over = 0;        // reprojection taps outside the valid state rectangle (tiled contexts)
@@ -981,13 +914,8 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
     // -4 %).  The other K1s hold too many registers for it (round 6,
     // profiles/r06_ab_keep_np.txt): the exact fit and f32 tmp_data spill at
     // four work-groups per CU and lose 7-8 % at three; config 5's half inputs
-    // (three registers per item, BMFR_KEEP_NP_HALF_IN) spill 7 dwords and tie.
-#ifdef BMFR_KEEP_NP_ALL
-    constexpr bool kKeepNP = true;
-#else
-    constexpr bool kKeepNP = FAST && (F32 ? BMFR_KEEP_NP_F32 && B < 16
-                                          : B < 16 || (BMFR_KEEP_NP_HALF_IN && sizeof(IN) == 2));
-#endif
+    // (three registers per item) spill 7 dwords and tie.
+    constexpr bool kKeepNP = FAST && !F32 && B < 16;
     KeptNP<IN> keep_np[NI];
     NoisyCur<IN> cur = noisy_load_current<IN>(P, A.in, bx * kEdge + lx, by * kEdge + item_row(l, 0), frame);
 #pragma unroll
@@ -1010,7 +938,6 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
                 if constexpr (F32) v = __builtin_isnan(v) ? 0.0f : v;
                 else v = __builtin_isnan(v) ? 0.0f : __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
                 if constexpr (kInterleave) {  // this item's half of its row-slot pair (XOR-swizzled as below)
-                    static_assert(!F32, "f32 tmp_data stores item pairs");
                     const int j = item_slot(i);
                     L.M[f - 1][l * kSlots + 2 * ((j >> 1) ^ ((l >> 2) & 7)) + (j & 1)] = (_Float16)v;
                 } else {
@@ -1039,11 +966,11 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
                     // rows 4 w + i - 1, 4 w + i: half (i - 1) / 2 of quad w; columns of
                     // wave w stay in registers, the others go to compacted quad
                     // w - (w > owner) of the owner's view (see Lds::M)
-                    static_assert(kIlv == 0, "f32 tmp_data: wave w computes row quad w");
+                    static_assert(!kInterleave, "f32 tmp_data: wave w computes row quad w");
 #pragma unroll
                     for (int f = 1; f < B; ++f) {
-                        const int ow = (f - 1) % NW;
-                        if (w == ow) own[(f - 1) / NW][i >> 1] = pk[f];
+                        const int ow = Fit::owner(f);
+                        if (w == ow) own[Fit::slot(f)][i >> 1] = pk[f];
                         else
                             *reinterpret_cast<f2v*>(&L.M[f - 1][l * m_slots<true>() + 4 * (w - (w > ow)) + (i - 1)]) =
                                 pk[f];
@@ -1062,14 +989,14 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
     }
     report_reach(P, A.reach, over);
     float pre[kPre][kSlots];
-    WaveFit<NS, FS, NW, FAST, F32>::prefetch_noise(w, l, A.noise, pre);
+    Fit::prefetch_noise(w, l, A.noise, pre);
     k1_barrier();  // matrix in LDS; phase 1's global stores drain in the background
     BMFR_STAMP(1);
     BMFR_STAMP(2);  // scaling runs inside the per-wave fit
 
     // ---- fit: min/max scaling, Householder QR, right-hand side ----
     if (t == 0) L.delay = P.debug_delay;  // read after the fit's barriers
-    WaveFit<NS, FS, NW, FAST, F32>::run(L, w, l, A.noise, pre, P.noise2, P.max_polls, kp, own);
+    Fit::run(L, w, l, A.noise, pre, P.noise2, P.max_polls, kp, own);
     // Phase 3's loads (normal and position of the NI items, bmfr.cl:725-729)
     // go out now: they land while wave 0 back-substitutes and the others wait.
     int l3 = l;  // opaque copy: recompute phase-1 addresses instead of keeping them live across the fit
@@ -1106,9 +1033,6 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
         wp[i] = widen(wp_r[i]);
     }
 
-#ifdef BMFR_PROBE_K1_NOP3  // timing probe (wrong results): no weighted sum / blend / stores
-    if (frame >= 0) return;
-#endif
     // ---- weighted_sum (bmfr.cl:717-750) + temporal blend (bmfr.cl:778-849) ----
     // Items (0, 1) and (2, 3) as packed f32 pairs: every lane rounds as
     // upstream's scalar sequence, each item in feature order.
@@ -1123,16 +1047,8 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
     // CU; pairs outer: none).  Features outer (each weight and min / max
     // loaded once) at B = 13, where the K1s have the registers for it since
     // round 6 (no spills; K1 -0.3 / -0.5 / -1.3 % headline / exact / f32
-    // tmp_data, profiles/r06_ab_np16.txt); -DBMFR_PAIRS_B13=1 keeps pairs
-    // outer there too.
-#ifndef BMFR_PAIRS_B13
-#define BMFR_PAIRS_B13 0
-#endif
-#ifdef PAIRS_ALL
-    constexpr bool kPairs = true;
-#else
-    constexpr bool kPairs = B >= 16 || (!COH && BMFR_PAIRS_B13) || NPR == 1;
-#endif
+    // tmp_data against pairs outer there too, profiles/r06_ab_np16.txt).
+    constexpr bool kPairs = B >= 16;
     constexpr int NH = kPairs ? NPR : 1;
 #pragma unroll
     for (int hh = 0; hh < NH; ++hh) {
@@ -1211,49 +1127,23 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
     }
 }
 
-// Waves per work-group of the column-split K1: 4, or 8 with -DBMFR_K1_WAVES=8
-// (half the rows per thread in phases 1 and 3, fewer columns per wave in the
-// fit, more waves per CU).
-#ifndef BMFR_K1_WAVES
-#define BMFR_K1_WAVES 4
-#endif
-constexpr int kNW = BMFR_K1_WAVES;
-constexpr int kK1Threads = 64 * kNW;
 // Minimum waves per SIMD for the register allocator: 4 work-groups of 4
-// waves per CU (128 VGPRs), or 3 of 8 (80); -DBMFR_K1_MIN_WAVES overrides.
-// f32 tmp_data: the compacted matrix's LDS allows four work-groups per CU at
-// B = 13 (38 KB each), three at B = 16 (48 KB); at B = 13 the exact fit
-// needs more than 128 VGPRs (78 spilled at four), so three there.
-#ifndef BMFR_F32_WAVES6
-#define BMFR_F32_WAVES6 4
-#endif
-#ifndef BMFR_F32_WAVES6X
-#define BMFR_F32_WAVES6X 3
-#endif
-#ifndef BMFR_F32_WAVES9
-#define BMFR_F32_WAVES9 3
-#endif
-#ifdef BMFR_K1_MIN_WAVES
-constexpr int kMinWavesSimd = BMFR_K1_MIN_WAVES;
-#else
-constexpr int kMinWavesSimd = kNW == 4 ? 4 : 6;
-#endif
-// Config 5 (B = 16, fast_fit): -DBMFR_K1_WAVES9F=5 asks for five work-groups
-// per CU (its LDS allows them since FitOut sits in the matrix area's tail).
-#ifndef BMFR_K1_WAVES9F
-#define BMFR_K1_WAVES9F kMinWavesSimd
-#endif
-template <int FS, bool F32, bool FAST>
+// waves per CU (128 VGPRs).  f32 tmp_data (fast_fit): the compacted matrix's
+// LDS allows four work-groups per CU at B = 13 (38 KB each), three at B = 16
+// (48 KB).  (Config 5 -- B = 16, half tmp_data, fast_fit -- has the LDS for
+// five work-groups per CU since FitOut sits in the matrix area's tail, but at
+// 96 VGPRs it spills 30: 0.4196 against 0.3438 ms/frame, round 5,
+// profiles/r05_ab_cfg5_waves.txt.)
+template <int FS, bool F32>
 constexpr int min_waves() {
-    return F32 ? (FS == 6 ? (FAST ? BMFR_F32_WAVES6 : BMFR_F32_WAVES6X) : BMFR_F32_WAVES9)
-               : (FS == 9 && FAST ? BMFR_K1_WAVES9F : kMinWavesSimd);
+    return F32 && FS == 9 ? 3 : 4;
 }
 
 // FAST: bmfr_config.fast_fit (the fused trailing update, update_column).
 template <int NS, int FS, class IN, bool FAST = false, bool F32 = false>
-__global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32, FAST>())) void k_fused_cols(Params P, K1Args A) {
-    __shared__ Lds<NS + FS + 3, kNW, F32> L;
-    k1_cols_body<NS, FS, IN, false, kNW, FAST, F32>(P, A, L, xcd_swizzle(blockIdx.x, gridDim.x));
+__global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32>())) void k_fused_cols(Params P, K1Args A) {
+    __shared__ Lds<NS + FS + 3, F32> L;
+    k1_cols_body<NS, FS, IN, false, FAST, F32>(P, A, L, xcd_swizzle(blockIdx.x, gridDim.x));
 }
 
 // K1 and K2 (64 x kFrameTaaH tiles) in one launch: work-groups [0, nk1) are K1
@@ -1270,15 +1160,15 @@ __global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32, FAST>())) void k_fu
 //     in order, so every K1 block a waiting tile needs has been dispatched:
 //     the waits end.
 template <int NS, int FS, class IN, bool SAME = false, bool FAST = false, bool F32 = false>
-__global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32, FAST>())) void k_fused_cols_taa(Params P, K1Args A, Params P2,
+__global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32>())) void k_fused_cols_taa(Params P, K1Args A, Params P2,
                                                                                     TaaArgs T, int nk1, int nk1p) {
     __shared__ union {
-        Lds<NS + FS + 3, kNW, F32> k1;
-        FrameTaaLds<kK1Threads> k2;
+        Lds<NS + FS + 3, F32> k1;
+        FrameTaaLds k2;
     } U;
     const int b = blockIdx.x;
-    if (b < nk1) k1_cols_body<NS, FS, IN, SAME, kNW, FAST, F32>(P, A, U.k1, xcd_swizzle(b, nk1));
-    else if (b >= nk1p) frame_taa_part<IN, SAME, kK1Threads>(P2, T, b, nk1p, U.k2);
+    if (b < nk1) k1_cols_body<NS, FS, IN, SAME, FAST, F32>(P, A, U.k1, xcd_swizzle(b, nk1));
+    else if (b >= nk1p) frame_taa_part<IN, SAME>(P2, T, b, nk1p, U.k2);
 }
 
 }  // namespace cols
@@ -1307,12 +1197,8 @@ namespace {
 // The column-split kernels' template arguments from the run-time parameters:
 // FS (6 or 9 scaled features), the input element type, fast_fit.
 // f32 tmp_data runs the exact fit row-split (bmfr_fused.hip: K1 -4 % against
-// the column split's, whose exact fit needs 145 VGPRs, three waves per SIMD)
-// unless -DBMFR_F32_COLS_EXACT=1; fast_fit column-split (K1 -8 %).
-#ifndef BMFR_F32_COLS_EXACT
-#define BMFR_F32_COLS_EXACT 0
-#endif
-constexpr bool kColsExact = !kColsF32 || BMFR_F32_COLS_EXACT;
+// a column-split exact fit, which needed 145 VGPRs, three waves per SIMD);
+// fast_fit column-split (K1 -8 %).
 
 // false (nothing launched): a configuration this translation unit has no
 // kernel for -- the f32 unit compiles only the fast fit, so a strict f32
@@ -1320,7 +1206,7 @@ constexpr bool kColsExact = !kColsF32 || BMFR_F32_COLS_EXACT;
 // the non-reference fit.
 template <template <int, class, bool> class L, class... Args>
 bool dispatch_cols(const Params& Q, Args&&... args) {
-    if constexpr (kColsExact) {
+    if constexpr (!kColsF32) {
         if (Q.scaled == 6) {
             if (Q.input_half) Q.fast_fit ? L<6, _Float16, true>::go(args...) : L<6, _Float16, false>::go(args...);
             else Q.fast_fit ? L<6, float, true>::go(args...) : L<6, float, false>::go(args...);
@@ -1348,7 +1234,7 @@ template <int FS, class IN, bool FAST>
 struct LaunchFrameOne {
     static void go(const Params& P, hipStream_t st, const FusedArgs& A) {
         const int nk1 = P.ring < 0 || P.nbx <= 0 || P.nby <= 0 ? 0 : k1_blocks(P), nk1p = (nk1 + 7) & ~7;
-        const int nk2 = frame_taa_tiles<cols::kK1Threads>(P);
+        const int nk2 = frame_taa_tiles(P);
         hipLaunchKernelGGL((cols::k_fused_cols_taa<4, FS, IN, true, FAST, kColsF32>), dim3(nk1p + nk2),
                            dim3(cols::kK1Threads), 0, st, P, k1_args(A), P, taa_args(A), nk1, nk1p);
     }
@@ -1358,7 +1244,7 @@ template <int FS, class IN, bool FAST>
 struct LaunchColsTaa {
     static void go(const Params& P, hipStream_t st, const FusedArgs* A, const Params& P2, const FusedArgs* A2) {
         const int nk1 = A ? k1_blocks(P) : 0, nk1p = (nk1 + 7) & ~7;
-        const int nk2 = A2 ? frame_taa_tiles<cols::kK1Threads>(P2) : 0;
+        const int nk2 = A2 ? frame_taa_tiles(P2) : 0;
         if (nk1 + nk2 == 0) return;
         const TaaArgs T = A2 ? taa_args(*A2) : TaaArgs{};
         hipLaunchKernelGGL((cols::k_fused_cols_taa<4, FS, IN, false, FAST, kColsF32>), dim3(nk2 ? nk1p + nk2 : nk1),
@@ -1388,14 +1274,8 @@ hipError_t launch_cols_k1_taa<kColsF32>(const Params& P, hipStream_t st, const F
 
 #if !BMFR_COLS_F32
 // f32 tmp_data with fast_fit runs the column-split K1 too
-// (bmfr_fused_cols_f32.hip); -DBMFR_F32_ROWS=1 keeps the row-split K1 of
-// bmfr_fused.hip for it (A/B).
-#ifndef BMFR_F32_ROWS
-#define BMFR_F32_ROWS 0
-#endif
-bool fused_cols_supported(const Params& P) {
-    return (P.half_tmp || (!BMFR_F32_ROWS && (P.fast_fit || BMFR_F32_COLS_EXACT))) && fused_supported(P);
-}
+// (bmfr_fused_cols_f32.hip); its exact fit is the row-split K1 of bmfr_fused.hip.
+bool fused_cols_supported(const Params& P) { return (P.half_tmp || P.fast_fit) && fused_supported(P); }
 
 bool seq_fused_supported(const Params& P) { return fused_cols_supported(P) && P.ring == 0; }
 // Untiled frames, a tiled context's whole frame and its border launch (the
@@ -1404,7 +1284,7 @@ bool seq_fused_supported(const Params& P) { return fused_cols_supported(P) && P.
 bool frame_fused_supported(const Params& P) { return fused_supported(P); }
 
 hipError_t launch_fused_frame_one(const Params& P, hipStream_t st, const FusedArgs& A) {
-    if (!fused_cols_supported(P)) return launch_fused_rows_frame_one(P, st, A);  // f32 tmp_data, BMFR_F32_ROWS
+    if (!fused_cols_supported(P)) return launch_fused_rows_frame_one(P, st, A);  // f32 tmp_data, exact fit
     return P.half_tmp ? launch_cols_frame_one<false>(P, st, A) : launch_cols_frame_one<true>(P, st, A);
 }
 

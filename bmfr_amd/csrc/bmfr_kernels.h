@@ -276,16 +276,9 @@ __device__ __forceinline__ NoisyCur<IN> noisy_load_current(const Params& P, cons
     NoisyCur<IN> c;
     item_pixel(P, gx, gy, frame, c.px, c.py, c.owner);
     const uint32_t lin = pix(P, c.px, c.py);
-#ifdef BMFR_PROBE_K1_NOCUR  // timing probe (wrong results): current planes from one pixel (cache hits)
-    const uint32_t l0 = lin & 63u;
-    c.wp = ld3raw<IN>(in.p_cur, l0);
-    c.nrm = ld3raw<IN>(in.n_cur, l0);
-    if constexpr (COLOUR) c.cur = ld3raw<IN>(in.noisy_cur, l0);
-#else
     c.wp = ld3raw<IN>(in.p_cur, lin);
     c.nrm = ld3raw<IN>(in.n_cur, lin);
     if constexpr (COLOUR) c.cur = ld3raw<IN>(in.noisy_cur, lin);
-#endif
     return c;
 }
 
@@ -294,12 +287,9 @@ __device__ __forceinline__ NoisyCur<IN> noisy_load_current(const Params& P, cons
 // reprojection (bmfr.cl:343-372) and issues the tap loads, _finish tests,
 // weighs and blends them (bmfr.cl:374-445).
 // Half input planes: previous position / normal taps loaded a row pair at a
-// time (noisy_taps_issue); -DBMFR_PAIR_TAPS=0 loads them pixel by pixel.
-#ifndef BMFR_PAIR_TAPS
-#define BMFR_PAIR_TAPS 1
-#endif
+// time (noisy_taps_issue); f32 planes pixel by pixel.
 template <class IN>
-constexpr bool kPairTaps = BMFR_PAIR_TAPS && sizeof(IN) == 2;
+constexpr bool kPairTaps = sizeof(IN) == 2;
 
 template <class IN = float>
 struct NoisyTaps {
@@ -409,19 +399,8 @@ __device__ __forceinline__ NoisyTaps<IN> noisy_taps_issue(const Params& P, const
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             tp.wts[i] = r.wts[i];
-            const uint32_t s = pix(P, clamp_rx(P, r.ix + (i & 1)), clamp_ry(P, r.iy + (i >> 1)));
-#ifdef BMFR_PROBE_K1_NOTAPS  // timing probe (wrong results): no previous-frame tap loads
-            (void)s;
-            tp.pp[i] = c.wp;
-            tp.pn[i] = c.nrm;
-            tp.pc[i] = f3{r.pfx, r.pfy, 0.f};
-            tp.spu[i] = i;
-            if (FILT) tp.pa[i] = f3{r.pfy, r.pfx, 0.f};
-#else
-            sidx[i] = s;
-#endif
+            sidx[i] = pix(P, clamp_rx(P, r.ix + (i & 1)), clamp_ry(P, r.iy + (i >> 1)));
         }
-#ifndef BMFR_PROBE_K1_NOTAPS
         if constexpr (kPairTaps<IN>) {
             // Half input planes: a tap row's two pixels (ix, y), (ix + 1, y) in
             // one 12-byte load per plane instead of two loads per pixel (a
@@ -442,9 +421,6 @@ __device__ __forceinline__ NoisyTaps<IN> noisy_taps_issue(const Params& P, const
                 tp.fix |= ((uint32_t)(sr < 0) << (2 * row)) | ((uint32_t)(sr > n - 2) << (2 * row + 1));
             }
             tp.any_fix = __builtin_amdgcn_ballot_w64(tp.fix != 0) != 0;
-#ifdef BMFR_PROBE_NO_PAIR_FIX  // test probe (wrong results at the plane's ends): tests/test_gpu_pair_taps.py
-            tp.any_fix = false;
-#endif
 #pragma unroll
             for (int row = 0; row < 2; ++row) tp.pq[row] = ld3pair_h(in.p_prev, spair[row]);
 #pragma unroll
@@ -463,7 +439,6 @@ __device__ __forceinline__ NoisyTaps<IN> noisy_taps_issue(const Params& P, const
 #pragma unroll
             for (int i = 0; i < 4; ++i) tp.pa[i] = ld3(acc_prev, sidx[i]);
         }
-#endif
     }
     return tp;
 }

@@ -110,27 +110,20 @@ __global__ __launch_bounds__(256) void k_taa(Params P, const float2* __restrict_
 // bmfr_taa_tile.h).
 // Tile height measured at 4K (K2 ms): 8: 0.114, 12: 0.105, 16: 0.112,
 // 24: 0.130, 32: 0.135; forcing 4 waves/SIMD (128 VGPRs) at 16: 0.159.
-// Round 4 (taps after the tone map, -DBMFR_K2_H / -DBMFR_K2_NT): 12: 0.1028,
-// 8 (80 VGPRs, six waves): 0.1028, 16: 0.1062, 512 threads x 16: 0.1074,
-// 512 x 24: 0.1190 (profiles/r04_ab_k2_shapes.txt).
-#ifndef BMFR_K2_H
-#define BMFR_K2_H 12
-#endif
-constexpr int kTaaW = 64, kTaaH = BMFR_K2_H;
-// Threads per tile (experiment: -DBMFR_K2_NT=384 / 768 -- 2 / 1 output
-// pixels per thread instead of 3, fewer registers, more waves per SIMD).
-#ifndef BMFR_K2_NT
-#define BMFR_K2_NT 256
-#endif
-constexpr int kTaaNT = BMFR_K2_NT;
+// Round 4 (taps after the tone map): 12: 0.1028, 8 (80 VGPRs, six waves):
+// 0.1028, 16: 0.1062, 512 threads x 16: 0.1074, 512 x 24: 0.1190
+// (profiles/r04_ab_k2_shapes.txt).
+constexpr int kTaaW = 64, kTaaH = 12;
+// Threads per tile: 256, three output pixels per thread (384 / 768 threads,
+// 2 / 1 pixels per thread with fewer registers and more waves per SIMD: K2
+// 0.1437 / 0.1198 against 0.1069 ms, round 3).
+constexpr int kTaaNT = kTileThreads;
 // Minimum waves per SIMD for the register allocator: six (80 VGPRs, no
 // spills since the strip resolve; K2 0.0989 -> 0.0980 ms against five,
 // profiles/r05_ab_k2.txt).
-#ifndef BMFR_K2_MINW
-#define BMFR_K2_MINW 6
-#endif
+constexpr int kTaaMinWaves = 6;
 template <class IN>
-__global__ __launch_bounds__(kTaaNT, BMFR_K2_MINW) void k_fused_taa(Params P, TaaArgs T) {
+__global__ __launch_bounds__(kTaaNT, kTaaMinWaves) void k_fused_taa(Params P, TaaArgs T) {
     __shared__ float4 Y[(kTaaW + 2) * (kTaaH + 2)];  // YCoCg (+ pad): one 16-byte read per neighbour
     __shared__ double sE[kPowrENum];
     __shared__ double2 sRP[kPowrRPNum];
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(kTaaNT, BMFR_K2_MINW) void k_fused_taa(Params P, Ta
     const int gi = xcd_swizzle(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
     const int bxi = gi % gridDim.x, byi = gi / gridDim.x;
     forward_reach(T, blockIdx.x == 0 && blockIdx.y == 0);
-    taa_tile<IN, kTaaH, false, kTaaNT, kStrip>(P, T, P.tx0 + bxi * kTaaW, P.ty0 + byi * kTaaH, Y, sE, sRP);
+    taa_tile<IN, kTaaH, false>(P, T, P.tx0 + bxi * kTaaW, P.ty0 + byi * kTaaH, Y, sE, sRP);
 }
 
 // ------------------------------------------------------------ halo copy --

@@ -133,27 +133,25 @@ __device__ __forceinline__ void forward_reach(const TaaArgs& T, bool here = true
     }
 }
 
-#ifndef BMFR_K2_STRIP
-#define BMFR_K2_STRIP 1
-#endif
-constexpr bool kStrip = BMFR_K2_STRIP;
+// Threads per tile: every kernel that runs tiles (k_fused_taa and the frame
+// kernels) has 256-thread work-groups.
+constexpr int kTileThreads = 256;
 
-// A tile's geometry: 64 x TH output pixels, NT threads (NT / 64 rows of 64
-// per pass, KN output pixels per thread), the tile and a 1-pixel ring in LDS.
-template <int TH, int NT, bool ST = false>
+// A tile's geometry: 64 x TH output pixels, kTileThreads threads (four rows
+// of 64, KN output pixels per thread), the tile and a 1-pixel ring in LDS.
+template <int TH>
 struct TileShape {
-    static constexpr int RP = NT / 64;  // tile rows per pass
+    static constexpr int RP = kTileThreads / 64;  // thread rows
     static_assert(TH % RP == 0 && TH >= RP, "tile height");
     static constexpr int HW = 64 + 2, HH = TH + 2, N = HW * HH;
     static constexpr int RING = N - 64 * TH;  // halo pixels
     static constexpr int KN = TH / RP;        // output pixels per thread
-    static_assert(RING <= NT, "one ring pixel per thread");
+    static_assert(RING <= kTileThreads, "one ring pixel per thread");
     // Tile row of thread row ty's k-th output pixel: a strip of KN
     // consecutive rows per thread (its KN 3x3 neighbourhoods overlap: one
-    // (KN + 2) x 3 window of LDS reads serves all of them), or with
-    // BMFR_K2_STRIP=0 rows ty, ty + RP, ... (a 3x3 read per pixel).  Either
-    // way a wave's loads and LDS accesses cover 64 consecutive pixels of a row.
-    static __device__ __forceinline__ int row(int ty, int k) { return ST ? ty * KN + k : ty + RP * k; }
+    // (KN + 2) x 3 window of LDS reads serves all of them, resolve_strip).
+    // A wave's loads and LDS accesses cover 64 consecutive pixels of a row.
+    static __device__ __forceinline__ int row(int ty, int k) { return ty * KN + k; }
 };
 
 // A thread's current-frame inputs of one tile, as loaded: the reprojected
@@ -167,9 +165,9 @@ struct TileLoads {
 };
 
 // This thread's ring pixel (t < RING), in tile + halo coordinates.
-template <int TH, int NT>
+template <int TH>
 __device__ __forceinline__ void ring_pixel(int t, int& hx, int& hy) {
-    using S = TileShape<TH, NT>;
+    using S = TileShape<TH>;
     if (t < 2 * S::HW) {
         hx = t % S::HW;
         hy = t < S::HW ? 0 : S::HH - 1;
@@ -181,10 +179,10 @@ __device__ __forceinline__ void ring_pixel(int t, int& hx, int& hy) {
 
 // Issue the tile's current-frame loads (reprojected positions first).  COH:
 // device-coherent loads of K1's outputs of the same launch.
-template <class IN, int TH, bool COH, int NT, bool ST>
+template <class IN, int TH, bool COH>
 __device__ __forceinline__ void tile_issue(const Params& P, const TaaArgs& T, int x0, int y0, int hx, int hy,
-                                           TileLoads<IN, TileShape<TH, NT>::KN>& L) {
-    using S = TileShape<TH, NT, ST>;
+                                           TileLoads<IN, TileShape<TH>::KN>& L) {
+    using S = TileShape<TH>;
     const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
     const CohPlane c_pp = coh_plane(T.prev_pixel), c_src = coh_plane(T.src);  // (unused unless COH)
 #pragma unroll
@@ -209,11 +207,11 @@ __device__ __forceinline__ void tile_issue(const Params& P, const TaaArgs& T, in
 
 // Tone map (bmfr.cl:851-856) of the loaded colours into the LDS window Y as
 // YCoCg; me[k]: this thread's own output pixels, tone-mapped RGB.
-template <class IN, int TH, int NT, bool ST>
-__device__ __forceinline__ void tile_tone(const Params& P, const TileLoads<IN, TileShape<TH, NT>::KN>& L, int hx,
+template <class IN, int TH>
+__device__ __forceinline__ void tile_tone(const Params& P, const TileLoads<IN, TileShape<TH>::KN>& L, int hx,
                                           int hy, float4* __restrict__ Y, const double* __restrict__ sE,
-                                          const double2* __restrict__ sRP, f3 (&me)[TileShape<TH, NT>::KN]) {
-    using S = TileShape<TH, NT, ST>;
+                                          const double2* __restrict__ sRP, f3 (&me)[TileShape<TH>::KN]) {
+    using S = TileShape<TH>;
     const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
     // The correctly rounded powr's table part for every channel of every
     // pixel, branch-free (gamma_table), so the compiler can issue a pixel's
@@ -228,14 +226,6 @@ __device__ __forceinline__ void tile_tone(const Params& P, const TileLoads<IN, T
         const f3 yc = rgb_to_ycocg(v);
         Y[ly * S::HW + lx] = make_float4(yc.x, yc.y, yc.z, 0.f);
     };
-#ifdef BMFR_PROBE_K2_NOTONE  // timing probe (wrong results): no tone map
-#pragma unroll
-    for (int k = 0; k <= S::KN; ++k) {
-        if (k == S::KN && t >= S::RING) break;
-        const f3 a = widen(L.al[k]);
-        put(k, f3{L.v[k].x * a.x, L.v[k].y * a.y, L.v[k].z * a.z});
-    }
-#else
     if (P.library_powr) {
 #pragma unroll
         for (int k = 0; k <= S::KN; ++k) {
@@ -256,7 +246,6 @@ __device__ __forceinline__ void tile_tone(const Params& P, const TileLoads<IN, T
             put(k, f3{g[0], g[1], g[2]});
         }
     }
-#endif
     if (__builtin_expect(rare != 0, 0)) {
 #pragma unroll
         for (int k = 0; k <= S::KN; ++k)
@@ -270,16 +259,11 @@ template <int KN>
 __device__ __forceinline__ void tile_taps(const Params& P, const TaaArgs& T, const float2 (&pf)[KN],
                                           f3 (&taps)[KN][4]) {
 #pragma unroll
-    for (int k = 0; k < KN; ++k) {
-#ifdef BMFR_PROBE_K2_NOTAPS  // timing probe (wrong results): no previous-frame taps
-        taps[k][0] = taps[k][1] = taps[k][2] = taps[k][3] = f3{pf[k].x, pf[k].y, 0.f};
-#else
-        taa_load_taps(P, pf[k], T.prev_frame, taps[k]);
-#endif
-    }
+    for (int k = 0; k < KN; ++k) taa_load_taps(P, pf[k], T.prev_frame, taps[k]);
 }
 
-// Strip form of the resolve (kStrip): the thread's KN output pixels are KN
+// The resolve of the tile's output pixels from the complete window Y
+// (bmfr.cl:897-973) and the stores.  The thread's KN output pixels are KN
 // consecutive rows of one column, so their 3x3 neighbourhoods lie in one
 // (KN + 2) x 3 window.  Each window row is read from LDS once and reduced to
 // its box bounds (min / max of its three values) and its centre value; a
@@ -288,12 +272,12 @@ __device__ __forceinline__ void tile_taps(const Params& P, const TaaArgs& T, con
 // sets of bmfr.cl:897-920, grouped differently (exact: taa_clamp_tail).
 // CHECK (tiles at the image border): out-of-image neighbours enter as +inf /
 // -inf, as in taa_clamp.
-template <int TH, int NT, bool CHECK>
+template <int TH, bool CHECK>
 __device__ __forceinline__ void resolve_strip(const Params& P, const TaaArgs& T, int x0, int y0,
-                                              const float4* __restrict__ Y, const f3 (&me)[TileShape<TH, NT>::KN],
-                                              const float2 (&pf)[TileShape<TH, NT>::KN],
-                                              const f3 (&hist)[TileShape<TH, NT>::KN]) {
-    using S = TileShape<TH, NT, true>;
+                                              const float4* __restrict__ Y, const f3 (&me)[TileShape<TH>::KN],
+                                              const float2 (&pf)[TileShape<TH>::KN],
+                                              const f3 (&hist)[TileShape<TH>::KN]) {
+    using S = TileShape<TH>;
     const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
     const int r0 = S::row(ty, 0);  // the window's first row is tile row r0 - 1
     struct Row {
@@ -329,9 +313,6 @@ __device__ __forceinline__ void resolve_strip(const Params& P, const TaaArgs& T,
         const Row w2 = reduce_row(k + 2);
         const int x = x0 + tx, y = y0 + r0 + k;
         if (x < P.tx1 && y < P.ty1) {
-#ifdef BMFR_PROBE_K2_NORESOLVE  // timing probe (wrong results): no TAA resolve
-            const f3 r{me[k].x + w1.mn.x + hist[k].x, me[k].y + w1.mx.y + hist[k].y, me[k].z + w2.clo.z};
-#else
             f3 r = me[k];
             if (!taa_offscreen(P, pf[k], T.frame)) {
                 const f3 mnb{mn4(w0.mn.x, w1.mn.x, w2.mn.x), mn4(w0.mn.y, w1.mn.y, w2.mn.y),
@@ -344,7 +325,6 @@ __device__ __forceinline__ void resolve_strip(const Params& P, const TaaArgs& T,
                              mx4(w0.chi.z, w1.mx.z, w2.chi.z)};
                 r = taa_clamp_tail(P, me[k], mnb, mxb, mnc, mxc, hist[k]);
             }
-#endif
             st3(T.result, pix(P, x, y), r);
         }
         w0 = w1;
@@ -352,46 +332,16 @@ __device__ __forceinline__ void resolve_strip(const Params& P, const TaaArgs& T,
     }
 }
 
-// The resolve of the tile's output pixels from the complete window Y
-// (bmfr.cl:897-973) and the stores.
-template <int TH, int NT, bool ST>
+// Tiles that reach the image border check every neighbour (bmfr.cl:901); the
+// others have all nine in the image.
+template <int TH>
 __device__ __forceinline__ void tile_resolve(const Params& P, const TaaArgs& T, int x0, int y0,
-                                             const float4* __restrict__ Y, const f3 (&me)[TileShape<TH, NT>::KN],
-                                             const float2 (&pf)[TileShape<TH, NT>::KN],
-                                             const f3 (&hist)[TileShape<TH, NT>::KN]) {
-    using S = TileShape<TH, NT, ST>;
-    const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
-    // Tiles that reach the image border check every neighbour (bmfr.cl:901);
-    // the others have all nine in the image.
+                                             const float4* __restrict__ Y, const f3 (&me)[TileShape<TH>::KN],
+                                             const float2 (&pf)[TileShape<TH>::KN],
+                                             const f3 (&hist)[TileShape<TH>::KN]) {
     const bool edge = x0 == 0 || y0 == 0 || x0 + 64 >= P.width || y0 + TH >= P.height;
-    if constexpr (ST) {
-        if (edge) resolve_strip<TH, NT, true>(P, T, x0, y0, Y, me, pf, hist);
-        else resolve_strip<TH, NT, false>(P, T, x0, y0, Y, me, pf, hist);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < S::KN; ++k) {
-        const int x = x0 + tx, y = y0 + S::row(ty, k);
-        if (x < P.tx1 && y < P.ty1) {
-            const int c = (S::row(ty, k) + 1) * S::HW + tx + 1;
-            f3 nb[9];
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const float4 q = Y[c + (j / 3 - 1) * S::HW + (j % 3 - 1)];
-                nb[j] = f3{q.x, q.y, q.z};
-            }
-#ifdef BMFR_PROBE_K2_NORESOLVE  // timing probe (wrong results): no TAA resolve
-            f3 r = me[k];
-#pragma unroll
-            for (int j = 0; j < 9; ++j) r = f3{r.x + nb[j].x, r.y + nb[j].y, r.z + nb[j].z};
-            r = f3{r.x + hist[k].x, r.y + hist[k].y, r.z + hist[k].z};
-#else
-            const f3 r = edge ? taa_clamp<true>(P, x, y, me[k], pf[k], nb, hist[k], T.frame)
-                              : taa_clamp<false>(P, x, y, me[k], pf[k], nb, hist[k], T.frame);
-#endif
-            st3(T.result, pix(P, x, y), r);
-        }
-    }
+    if (edge) resolve_strip<TH, true>(P, T, x0, y0, Y, me, pf, hist);
+    else resolve_strip<TH, false>(P, T, x0, y0, Y, me, pf, hist);
 }
 
 // One tile.  Y: (64 + 2) * (TH + 2) float4; sE / sRP: the powr tables' LDS
@@ -401,60 +351,56 @@ __device__ __forceinline__ void tile_resolve(const Params& P, const TaaArgs& T, 
 // taps (their latency under the barrier), each pixel's history as its taps
 // arrive (three values live instead of twelve: 89 VGPRs, five waves per
 // SIMD, where taps issued before the tone map held 124), the resolve.
-template <class IN, int TH, bool COH = false, int NT = 256, bool ST = false>
+template <class IN, int TH, bool COH = false>
 __device__ __forceinline__ void taa_tile(const Params& P, const TaaArgs& T, int x0, int y0, float4* __restrict__ Y,
                                          double* __restrict__ sE, double2* __restrict__ sRP) {
-    using S = TileShape<TH, NT>;
+    using S = TileShape<TH>;
     constexpr int KN = S::KN;
     const int t = threadIdx.x;
-    bmfr_powr_tables_to_lds<NT>(sE, sRP, t);
+    bmfr_powr_tables_to_lds<kTileThreads>(sE, sRP, t);
     if constexpr (COH) wait_k1_blocks(P, T, x0, y0, TH);
     int hx = 0, hy = 0;
-    ring_pixel<TH, NT>(t, hx, hy);
+    ring_pixel<TH>(t, hx, hy);
     TileLoads<IN, KN> L;
-    tile_issue<IN, TH, COH, NT, ST>(P, T, x0, y0, hx, hy, L);
+    tile_issue<IN, TH, COH>(P, T, x0, y0, hx, hy, L);
     __syncthreads();  // the powr tables are in LDS
     f3 me[KN];
-    tile_tone<IN, TH, NT, ST>(P, L, hx, hy, Y, sE, sRP, me);
+    tile_tone<IN, TH>(P, L, hx, hy, Y, sE, sRP, me);
     f3 taps[KN][4];
     tile_taps<KN>(P, T, L.pf, taps);
     __syncthreads();  // the window is complete
     f3 hist[KN];
 #pragma unroll
     for (int k = 0; k < KN; ++k) hist[k] = taa_history(P, L.pf[k], taps[k]);
-    tile_resolve<TH, NT, ST>(P, T, x0, y0, Y, me, L.pf, hist);
+    tile_resolve<TH>(P, T, x0, y0, Y, me, L.pf, hist);
 }
 
 // The TAA part of a one-launch frame kernel (K1 blocks, then the frame's
 // TAA tiles; bmfr_fused_cols.hip k_fused_cols_taa, bmfr_fused.hip
-// k_fused_rows_taa) of NT threads per work-group: work-group b >= nk1p of
-// the launch is tile b - nk1p (64 x frame_taa_h<NT>, XCD-aware order).
+// k_fused_rows_taa): work-group b >= nk1p of the launch is tile b - nk1p
+// (64 x kFrameTaaH, XCD-aware order).
 // COH: the tiles wait for the K1 blocks of the same launch; a tiled
 // context's last work-group then forwards the reach report once every K1
 // block of the launch has raised it.
-template <int NT>
-// Tile height of the one-launch frame's TAA tiles at 256 threads: 16 (four
-// output rows per thread; no spills beside K1's registers) against 12: 1080p
-// frame -1.2 % (fast_fit), -2.1 % (config 5), -0.4 % (exact); 8: +5 %; 20: 1
-// dword of spills, -0.8 %; 24: spills (round 6, profiles/r06_ab_frame_taa_h.txt).
-// The standalone K2 keeps 64 x 12 (BMFR_K2_H): its occupancy is its own.
-#ifndef BMFR_FRAME_TAA_H
-#define BMFR_FRAME_TAA_H 16
-#endif
-constexpr int frame_taa_h() { return NT == 256 ? BMFR_FRAME_TAA_H : 24; }  // TH / 4 output rows per thread
-template <int NT>
+//
+// Tile height of the one-launch frame's TAA tiles: 16 (four output rows per
+// thread; no spills beside K1's registers) against 12: 1080p frame -1.2 %
+// (fast_fit), -2.1 % (config 5), -0.4 % (exact); 8: +5 %; 20: 1 dword of
+// spills, -0.8 %; 24: spills (round 6, profiles/r06_ab_frame_taa_h.txt).
+// The standalone K2 keeps 64 x 12 (kTaaH, bmfr_kernels.hip): its occupancy is
+// its own.
+constexpr int kFrameTaaH = 16;
 struct FrameTaaLds {
-    float4 Y[(64 + 2) * (frame_taa_h<NT>() + 2)];
+    float4 Y[(64 + 2) * (kFrameTaaH + 2)];
     double sE[kPowrENum];
     double2 sRP[kPowrRPNum];
 };
-template <class IN, bool COH, int NT>
-__device__ __forceinline__ void frame_taa_part(const Params& P2, const TaaArgs& T, int b, int nk1p,
-                                               FrameTaaLds<NT>& L) {
-    constexpr int TH = frame_taa_h<NT>();
+template <class IN, bool COH>
+__device__ __forceinline__ void frame_taa_part(const Params& P2, const TaaArgs& T, int b, int nk1p, FrameTaaLds& L) {
+    constexpr int TH = kFrameTaaH;
     const int gx = (P2.tx1 - P2.tx0 + 63) / 64, n2 = (int)gridDim.x - nk1p;
     const int gi = xcd_swizzle(b - nk1p, n2);
-    taa_tile<IN, TH, COH, NT, kStrip>(P2, T, P2.tx0 + (gi % gx) * 64, P2.ty0 + (gi / gx) * TH, L.Y, L.sE, L.sRP);
+    taa_tile<IN, TH, COH>(P2, T, P2.tx0 + (gi % gx) * 64, P2.ty0 + (gi / gx) * TH, L.Y, L.sE, L.sRP);
     if constexpr (COH) {
         if (T.reach_dev && b == (int)gridDim.x - 1) {
             wait_all_k1_blocks(P2, T);
@@ -462,9 +408,8 @@ __device__ __forceinline__ void frame_taa_part(const Params& P2, const TaaArgs& 
         }
     }
 }
-template <int NT>
 inline int frame_taa_tiles(const Params& P) {
-    constexpr int TH = frame_taa_h<NT>();
+    constexpr int TH = kFrameTaaH;
     return ((P.tx1 - P.tx0 + 63) / 64) * ((P.ty1 - P.ty0 + TH - 1) / TH);
 }
 

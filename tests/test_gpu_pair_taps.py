@@ -12,9 +12,8 @@ and the right / left ends of an inner row, one per frame, each on the
 bit-exact path with half inputs against the reference kernels (strict build,
 inputs widened) -- every buffer of the state and the output bit for bit; the
 same input planes every frame, so each corner pixel accepts the tap at its
-own position, the one the fix-up supplies.  (A build without the fix-up,
--DBMFR_PROBE_NO_PAIR_FIX, fails here at frame 1: 251 of 30,720 output values
-differ.)
+own position, the one the fix-up supplies.  (A build with the fix-up
+disabled failed here at frame 1: 251 of 30,720 output values differed.)
 """
 from __future__ import annotations
 
