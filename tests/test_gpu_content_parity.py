@@ -1,0 +1,431 @@
+"""Parity on content the synthetic sequence cannot produce (tests/scenes_np.py;
+tests/test_scenes_np.py shows on the CPU oracle what each scene reaches):
+
+  pan    16 px/frame there and back: accept masks 0 / 15 and the mixed ones at
+         the quad's edges, taps clamped at ix = -2 and ix = W + 1
+  far    a flat wall with every coordinate near 16: collinear feature
+         columns, both arms of scale() in one frame
+  rand   all 16 accept masks, every popcount on >= 1 % of the pixels
+  clamp  NaN normals (the NaN -> 0 guard of the design matrix), positions
+         beyond half's range once squared / cubed (the +-65504 clamp, half
+         tmp_data only), a reprojection thrown to |pf| ~ 1e7 (the float
+         clamp before the tap index); f32 tmp_data runs clamp_nan, the
+         variant without the out-of-range positions
+
+at the sizes of REF_CONFIGS entries, so the CPU oracle and both builds of the
+reference kernels exist; 6 frames each.
+
+Exact path, bit for bit: stages == oracle, stages (library powr) ==
+reference strict build, on every inter-stage buffer; the fused frame (one
+launch, two launches, one process_sequence call) == stages; half input
+planes == the widened planes == the reference on the widened planes.
+clamp compares NaN-aware (same NaN positions, everything else bit for bit);
+every other scene is asserted finite and compared strictly.
+
+fast_fit: the frame output within relative L2 1e-4 of the reference's strict
+and default builds per frame, the temporal state the fit does not feed bit
+for bit, and a per-tile worst case: over every 32x32 image-aligned tile (at
+most four fit blocks) and frame, the relative L2 against the strict build of
+(a) fast_fit and (b) the reference's own default build; max (a) <= 4 max (b).
+The yardstick is the reference's build-to-build distance on the same tiles,
+the factor the largest ratio of the two at frame level in the project's
+records rounded up (fast_fit 3.8e-5 in config 5 against 1.2e-5).  Both
+maxima go to the parity log as content_<scene>_<case>
+(profiles/content_parity.json).  One case misses the per-tile bar and is a
+strict expected failure of that bar alone: far at B = 16 with half tmp_data
+(KNOWN_TILE_MISS below has the figures and what is known of the cause).
+
+Tiled half inputs: 320x256 as 2x1 and 1x2 tiles, halo 40, half input planes
+cut from the generator's frame, exact path and fast_fit == the untiled
+half-input frames bit for bit, the halo report clean, with pan's taps
+crossing the internal tile edge in both directions.  A halo of 40 covers 6 px
+of motion per frame (tile_halo - 34), so pan runs at a fifth of its speed
+there (3.3 px/frame on the wall, up to 5.5 on the quad).
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+import torch
+
+import bmfr_amd
+import pyoracle
+import ref_run
+import scenes_np
+from ref_configs import REF_CONFIGS
+from seq_util import ALL_KEYS, compare_exact, to_np
+
+pytestmark = pytest.mark.gpu
+
+FRAMES = 6
+SEED = 2   # tests/test_scenes_np.py asserts the coverage for this seed
+TOL = 1e-4  # north_star: "within 1e-4 relative L2 of the OpenCL reference" (tests/test_gpu_fast_fit.py)
+TILE_FACTOR = 4.0
+PLANES = ("noisy", "normals", "positions", "albedo")
+CANONICAL = ("s128x80_h13", "s128x80_f13", "s100x72_h16", "s96x64_f16")
+GENERIC = ("s96x64_h7", "s80x64_h12")
+CASES = [(s, n) for s in ("pan", "far", "rand", "clamp") for n in CANONICAL] + \
+        [(s, n) for s in ("rand", "clamp") for n in GENERIC]
+# record key -> bmfr_state plane.  (The fused kernel keeps the accept bits in registers -- bmfr_state
+# reports no accept plane -- so they are compared through what they decide: spp and both accumulations.)
+FUSED_KEYS = {"result": "result", "noisy": "noisy_accumulated", "acc": "filtered_accumulated", "spp": "spp",
+              "prev_pixel": "prev_frame_pixel"}
+
+
+def content(scene: str, name: str) -> str:
+    """f32 tmp_data has no +-65504 clamp: it gets clamp without the out-of-range positions."""
+    return "clamp_nan" if scene == "clamp" and not REF_CONFIGS[name].half_tmp else scene
+
+
+def _dev(a):
+    return torch.from_numpy(np.array(a, order="C")).cuda()  # a copy: the generator's planes are read-only
+
+
+def through_half(a: np.ndarray) -> np.ndarray:
+    return a.astype(np.float16).astype(np.float32)
+
+
+def bmfr_cfg(rc, **kw) -> bmfr_amd.BmfrConfig:
+    return bmfr_amd.BmfrConfig(image_width=rc.width, image_height=rc.height, not_scaled=rc.not_scaled,
+                               scaled=rc.scaled, use_half_precision_in_tmp_data=rc.half_tmp,
+                               position_limit_squared=rc.position_limit_squared,
+                               normal_limit_squared=rc.normal_limit_squared, **kw)
+
+
+def _floats(a: np.ndarray):
+    if a.dtype == np.uint16:  # half buffers travel as their bits (seq_util.to_np)
+        return a.view(np.float16)
+    return a if a.dtype.kind == "f" else None
+
+
+def compare_nan_aware(got, ref, keys, where=""):
+    """Equal when the NaN positions are the same set and every other element,
+    infinities included, has the same bits."""
+    for f, (g, r) in enumerate(zip(got, ref)):
+        for k in keys:
+            a, b = g[k].reshape(-1), r[k].reshape(-1)
+            assert a.shape == b.shape and a.dtype == b.dtype, (where, f, k, a.shape, b.shape)
+            fa, fb = _floats(a), _floats(b)
+            if fa is None:
+                bad = np.flatnonzero(a != b)
+            else:
+                na, nb = np.isnan(fa), np.isnan(fb)
+                assert (na == nb).all(), f"{where} frame {f} {k}: NaN at {int(na.sum())} vs {int(nb.sum())} places, " \
+                                         f"first difference at {np.flatnonzero(na != nb)[:5]}"
+                bits = {2: np.uint16, 4: np.uint32}[a.dtype.itemsize]
+                bad = np.flatnonzero((a.view(bits) != b.view(bits)) & ~na)
+            assert bad.size == 0, f"{where} frame {f} {k}: {bad.size} of {a.size} differ, first at {bad[:5]}: " \
+                                  f"{a[bad[:5]]} vs {b[bad[:5]]}"
+
+
+def assert_finite(frames, keys, where=""):
+    for f, g in enumerate(frames):
+        for k in keys:
+            v = _floats(g[k])
+            assert v is None or np.isfinite(v).all(), (where, f, k)
+
+
+def compare(scene, got, ref, keys, where):
+    if scene == "clamp":
+        compare_nan_aware(got, ref, keys, where)
+    else:
+        assert_finite(ref, keys, where + " (reference)")
+        compare_exact(got, ref, keys, where)
+
+
+_cache = {}
+
+
+def cached(key, make):
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+def need_ref(name, mode="strict"):
+    if not ref_run.available(name, mode):
+        pytest.fail(f"reference build {name}_{mode} missing (oracle/build_ref.py)")
+
+
+def ref_frames(scene, name, mode="strict", half_in=False):
+    need_ref(name, mode)
+    rc = REF_CONFIGS[name]
+    return cached((scene, name, "ref", mode, half_in), lambda: scenes_np.run_loop(
+        ref_run.RefLoop(rc, mode), content(scene, name), rc.width, rc.height, FRAMES, SEED, to_device=_dev,
+        sync=torch.cuda.synchronize, prepare=through_half if half_in else None))
+
+
+def oracle_frames(scene, name):
+    rc = REF_CONFIGS[name]
+    cfg = pyoracle.make_cfg(rc.width, rc.height, rc.not_scaled, rc.scaled, rc.half_tmp)
+    return cached((scene, name, "oracle"), lambda: scenes_np.run_loop(
+        pyoracle.OracleLoop(cfg), content(scene, name), rc.width, rc.height, FRAMES, SEED))
+
+
+def stage_frames(scene, name, library_powr):
+    rc = REF_CONFIGS[name]
+    return cached((scene, name, "stages", library_powr), lambda: scenes_np.run_loop(
+        bmfr_amd.StagePipeline(bmfr_cfg(rc, library_powr=library_powr)), content(scene, name), rc.width, rc.height,
+        FRAMES, SEED, to_device=_dev, sync=torch.cuda.synchronize))
+
+
+def device_frames(scene, name, half_in=False):
+    """Per frame: (planes on the device, previous camera, jitter)."""
+    rc = REF_CONFIGS[name]
+
+    def make():
+        out = []
+        for f in range(FRAMES):
+            fr = scenes_np.frame(content(scene, name), rc.width, rc.height, f, SEED)
+            planes = {k: _dev(fr[k].astype(np.float16) if half_in else fr[k]) for k in PLANES}
+            out.append((planes, fr["prev_vp"], fr["jitter"]))
+        return out
+    return cached((scene, name, "device", half_in), make)
+
+
+def fused_state(den, n):
+    f32 = lambda m: torch.empty(m, device="cuda")  # noqa: E731
+    u8 = lambda m: torch.empty(m, dtype=torch.uint8, device="cuda")  # noqa: E731
+    out = {"result": den.copy_output(f32(3 * n))}
+    for k, name in FUSED_KEYS.items():
+        if k != "result":
+            out[k] = den.copy_state(name, u8(n) if k == "spp" else f32((2 if k == "prev_pixel" else 3) * n))
+    torch.cuda.synchronize()
+    return {k: to_np(v).copy() for k, v in out.items()}
+
+
+def fused_frames(scene, name, profiled=False, half_in=False, **kw):
+    """The production frame path, frame by frame: one launch per frame, or
+    (profiled: per-kernel events) K1 and K2 as two launches."""
+    rc = REF_CONFIGS[name]
+
+    def make():
+        den = bmfr_amd.Denoiser(bmfr_cfg(rc, input_half=int(half_in), **kw))
+        if profiled:
+            den.set_profiling(True, capacity=FRAMES, stride=1)
+        out = []
+        for f, (p, vp, jit) in enumerate(device_frames(scene, name, half_in)):
+            den.process_frame(p["noisy"], p["normals"], p["positions"], p["albedo"], vp, jit, f)
+            out.append(fused_state(den, rc.width * rc.height))
+        return out
+    return cached((scene, name, "fused", profiled, half_in, tuple(sorted(kw.items()))), make)
+
+
+def ids(cases):
+    return ["-".join(str(v) for v in c) for c in cases]
+
+
+@pytest.mark.parametrize("scene,name", CASES, ids=ids(CASES))
+def test_stages_match_oracle(scene, name, gpu):
+    """Default (correctly rounded) powr: every buffer equals the CPU oracle's."""
+    compare(scene, stage_frames(scene, name, 0), oracle_frames(scene, name), ALL_KEYS,
+            f"HIP stages vs oracle[{scene} {name}]")
+
+
+@pytest.mark.parametrize("scene,name", CASES, ids=ids(CASES))
+def test_stages_match_reference_strict(scene, name, gpu):
+    """library_powr: the reference kernel's own powr, so every buffer is pinned."""
+    compare(scene, stage_frames(scene, name, 1), ref_frames(scene, name), ALL_KEYS,
+            f"HIP stages vs reference[{scene} {name}]")
+
+
+@pytest.mark.parametrize("library_powr", [0, 1])
+@pytest.mark.parametrize("scene,name", CASES, ids=ids(CASES))
+def test_fused_frame_matches_stages(scene, name, library_powr, gpu):
+    rc = REF_CONFIGS[name]
+    st = stage_frames(scene, name, library_powr)
+    one = fused_frames(scene, name, library_powr=library_powr)
+    two = fused_frames(scene, name, profiled=True, library_powr=library_powr)
+    compare(scene, one, st, tuple(FUSED_KEYS), f"one launch vs stages[{scene} {name}]")
+    compare(scene, two, st, tuple(FUSED_KEYS), f"two launches vs stages[{scene} {name}]")
+    frames = device_frames(scene, name)
+    den = bmfr_amd.Denoiser(bmfr_cfg(rc, library_powr=library_powr))
+    outs = [torch.empty(3 * rc.width * rc.height, device="cuda") for _ in range(FRAMES)]
+    den.process_sequence([p for p, _, _ in frames], [(vp, jit) for _, vp, jit in frames], 0, outputs=outs)
+    torch.cuda.synchronize()
+    compare(scene, [{"result": to_np(o)} for o in outs], [{"result": g["result"]} for g in one], ("result",),
+            f"sequence vs per-frame[{scene} {name}]")
+
+
+HALF_CASES = [(s, n) for s in ("pan", "rand", "clamp") for n in ("s128x80_h13", "s100x72_h16")]
+
+
+@pytest.mark.parametrize("scene,name", HALF_CASES, ids=ids(HALF_CASES))
+def test_half_inputs_match_widened_and_reference(scene, name, gpu):
+    """Half input planes (the paired 12-byte tap loads) through every accept
+    mask and the clamped off-image tap indices."""
+    rc = REF_CONFIGS[name]
+    half = fused_frames(scene, name, half_in=True, library_powr=1)
+    # the same Denoiser on the widened planes
+    den = bmfr_amd.Denoiser(bmfr_cfg(rc, library_powr=1))
+    wide = []
+    for f, (p, vp, jit) in enumerate(device_frames(scene, name, half_in=True)):
+        w = {k: v.float() for k, v in p.items()}
+        den.process_frame(w["noisy"], w["normals"], w["positions"], w["albedo"], vp, jit, f)
+        wide.append(fused_state(den, rc.width * rc.height))
+    compare(scene, half, wide, tuple(FUSED_KEYS), f"half vs widened[{scene} {name}]")
+    compare(scene, half, ref_frames(scene, name, "strict", half_in=True), tuple(FUSED_KEYS),
+            f"half vs reference on widened[{scene} {name}]")
+    # the half path really read half planes
+    f32 = fused_frames(scene, name, library_powr=1)
+    assert half[-1]["result"].tobytes() != f32[-1]["result"].tobytes()
+
+
+def rel_l2_finite(a, b, where):
+    """Relative L2 over the elements finite in the reference b; the
+    non-finite positions must coincide."""
+    fa, fb = np.isfinite(a), np.isfinite(b)
+    assert (fa == fb).all(), (where, int((~fa).sum()), int((~fb).sum()))
+    a, b = a[fb].astype(np.float64), b[fb].astype(np.float64)
+    n = np.linalg.norm(b)
+    return float(np.linalg.norm(a - b) / n) if n > 0 else None
+
+
+def worst_tile(frames, ref, W, H):
+    """(worst relative L2, frame, tile x, tile y) over the 32x32 image-aligned
+    tiles of `result`; tiles whose reference norm is zero are skipped."""
+    worst = (0.0, -1, -1, -1)
+    for f, (g, r) in enumerate(zip(frames, ref)):
+        a, b = g["result"].reshape(H, W, 3), r["result"].reshape(H, W, 3)
+        for ty in range(0, H, 32):
+            for tx in range(0, W, 32):
+                e = rel_l2_finite(a[ty:ty + 32, tx:tx + 32], b[ty:ty + 32, tx:tx + 32], (f, tx, ty))
+                if e is not None and e > worst[0]:
+                    worst = (e, f, tx, ty)
+    return worst
+
+
+# (case id, reference configuration, half input planes): the configurations fast_fit supports
+FAST = {"h13": ("s128x80_h13", False), "f13": ("s128x80_f13", False), "h16": ("s100x72_h16", False),
+        "h16_in16": ("s100x72_h16", True)}
+FAST_CASES = [(s, c) for s in ("pan", "far", "rand", "clamp") for c in FAST]
+# The one case that misses a bar.  Measured on an MI355X: the per-frame bars hold (worst 1.58e-5 of
+# the strict build, 1.68e-5 of the default build), the per-tile bar does not: fast_fit's worst tile
+# is 7.64e-5 (frame 0, the 4-pixel-wide tile at x = 96, y = 64) against 1.78e-5 for the reference's
+# own default build (frame 0, tile x = 0, y = 32) -- 4.3 x, the bar is 4 x.  What is known
+# (tools/content_far_probe.py, profiles/content_far_probe.txt): the excess sits in the narrow tiles
+# at the right image edge, which show one or two blocks where a full tile averages four, on every
+# frame; the same wall, image and block grid with the positions 8 or 15 units nearer the origin
+# stay at 1-2e-5 in every tile, as do B = 13 and a width that is a multiple of 32 -- so it follows
+# the magnitude of the position values (x^3 ~ 5000 in half tmp_data), not a pixel or block index:
+# rounding in fast_fit's arithmetic, not its logic.  Which operation carries it was not isolated;
+# the exact path's own response to one-ulp changes of the noisy input is not raised in those tiles.
+# With half input planes the reference's two builds are themselves 1.03e-4 apart on a tile of this scene.
+KNOWN_TILE_MISS = {
+    ("far", "h16"): "fast_fit's worst 32x32 tile 7.64e-5 of the strict build (frame 0, tile 96,64) against 1.78e-5 "
+                    "between the reference's builds (frame 0, tile 0,32): 4.3 x, bar 4 x; per-frame 1.58e-5 / "
+                    "1.68e-5, within 1e-4.  Follows the magnitude of the positions (gone 8 units nearer the "
+                    "origin, same image and blocks): inherent in fast_fit's arithmetic at B = 16 with half "
+                    "tmp_data near the 16-unit bound"}
+
+
+class TileBarMissed(AssertionError):
+    """The per-tile bar alone: the expected failure covers nothing else."""
+
+
+FAST_PARAMS = [pytest.param(*c, id="-".join(c), marks=[pytest.mark.xfail(strict=True, raises=TileBarMissed,
+                                                                         reason=KNOWN_TILE_MISS[c])]
+                            if c in KNOWN_TILE_MISS else []) for c in FAST_CASES]
+
+
+@pytest.mark.parametrize("scene,case", FAST_PARAMS)
+def test_fast_fit_within_tolerance(scene, case, gpu, parity_log):
+    name, half_in = FAST[case]
+    rc = REF_CONFIGS[name]
+    W, H = rc.width, rc.height
+    need_ref(name, "default")
+    fast = fused_frames(scene, name, half_in=half_in, library_powr=1, fast_fit=1)
+    strict = ref_frames(scene, name, "strict", half_in)
+    default = ref_frames(scene, name, "default", half_in)
+    where = f"fast_fit[{scene} {case}]"
+    e_strict = [rel_l2_finite(g["result"], r["result"], where) for g, r in zip(fast, strict)]
+    e_default = [rel_l2_finite(g["result"], r["result"], where) for g, r in zip(fast, default)]
+    builds = [rel_l2_finite(d["result"], r["result"], where) for d, r in zip(default, strict)]
+    tile_fast, tile_builds = worst_tile(fast, strict, W, H), worst_tile(default, strict, W, H)
+    parity_log(f"content_{scene}_{case}", {
+        "scene": content(scene, name), "config": name, "input_half": int(half_in), "frames": FRAMES,
+        "fast_fit_vs_strict_per_frame": [float(f"{e:.3e}") for e in e_strict],
+        "fast_fit_vs_default_per_frame": [float(f"{e:.3e}") for e in e_default],
+        "default_vs_strict_per_frame": [float(f"{e:.3e}") for e in builds],
+        "worst_tile_fast_fit": {"rel_l2": float(f"{tile_fast[0]:.3e}"), "frame": tile_fast[1],
+                                "tile": list(tile_fast[2:])},
+        "worst_tile_default_build": {"rel_l2": float(f"{tile_builds[0]:.3e}"), "frame": tile_builds[1],
+                                     "tile": list(tile_builds[2:])}})
+    print(f"{where}: frame worst vs strict {max(e_strict):.3e}, vs default {max(e_default):.3e}, builds "
+          f"{max(builds):.3e}; tile worst fast {tile_fast}, builds {tile_builds}")
+    # the fit does not feed these
+    compare(scene, fast, strict, ("noisy", "spp", "prev_pixel"), where)
+    if scene != "clamp":
+        assert_finite(fast, ("result", "acc"), where)
+    # the reference's default build is itself beyond 1e-4 of its strict build with B = 16 and half
+    # tmp_data (tests/test_gpu_parity.py test_against_reference_default_build): that bar there
+    bar_default = 1.5e-4 if rc.half_tmp and rc.buffer_count == 16 and max(builds) > TOL else TOL
+    assert max(e_strict) <= TOL, (where, e_strict)
+    assert max(e_default) <= bar_default, (where, e_default, bar_default)
+    if not tile_fast[0] <= TILE_FACTOR * tile_builds[0]:
+        raise TileBarMissed((where, tile_fast, tile_builds))
+
+
+@pytest.mark.parametrize("fast_fit", [0, 1], ids=["exact", "fast_fit"])
+@pytest.mark.parametrize("scene", ["pan", "rand"])
+@pytest.mark.parametrize("gx,gy", [(2, 1), (1, 2)], ids=["2x1", "1x2"])
+def test_tiled_half_inputs_match_untiled(gx, gy, scene, fast_fit, gpu):
+    """Tiled contexts have non-zero plane origins and region-sized planes:
+    the paired half tap loads there, against the untiled half-input frame."""
+    from bmfr_amd.tiling import HipCopier, LoopbackTransport, TileGrid, state_planes
+    W, H, halo = 320, 256, 40
+    n = W * H
+    # a halo of 40 covers 6 px of motion (include/bmfr.h: tile_halo - 34): the pan at a fifth of
+    # its speed, 3.3 px/frame on the wall and up to 5.5 on the quad (1.7 x the parallax); rand
+    # moves up to 5.9 px at this size
+    speed = 0.2 if scene == "pan" else 1.0
+    grid = TileGrid(W, H, gx, gy, halo=halo)
+    kw = dict(image_width=W, image_height=H, input_half=1, fast_fit=fast_fit)
+    full = bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(**kw))
+    tiles = [bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(tile=grid.tile(r), tile_halo=halo, **kw))
+             for r in range(grid.ranks)]
+    loop, copier = LoopbackTransport(grid), HipCopier()
+    prev = [None] * grid.ranks
+    crossed = [False] * grid.ranks
+    for f in range(FRAMES):
+        fr = scenes_np.frame(scene, W, H, f, SEED, speed=speed)
+        vp, jit = fr["prev_vp"], fr["jitter"]
+        p = {k: _dev(fr[k].astype(np.float16)) for k in PLANES}
+        full.process_frame(p["noisy"], p["normals"], p["positions"], p["albedo"], vp, jit, f)
+        inps = []
+        for d in tiles:
+            cut = scenes_np.frame(scene, W, H, f, SEED, region=d.region, speed=speed)
+            inps.append({k: _dev(cut[k].astype(np.float16)) for k in PLANES})
+        if f > 0:
+            loop.exchange_all([state_planes(d) for d in tiles], copier)
+        for r, d in enumerate(tiles):
+            i = inps[r]
+            d.process_frame(i["noisy"], i["normals"], i["positions"], i["albedo"], vp, jit, f,
+                            prev_normals=prev[r]["normals"] if prev[r] else None,
+                            prev_positions=prev[r]["positions"] if prev[r] else None)
+        prev = inps
+        torch.cuda.synchronize()
+        want = {"result": full.copy_output(torch.empty(3 * n, device="cuda")).view(H, W, 3),
+                "filtered_accumulated": full.copy_state("filtered_accumulated",
+                                                        torch.empty(3 * n, device="cuda")).view(H, W, 3),
+                "noisy_accumulated": full.copy_state("noisy_accumulated",
+                                                     torch.empty(3 * n, device="cuda")).view(H, W, 3)}
+        pp = full.copy_state("prev_frame_pixel", torch.empty(2 * n, device="cuda")).view(H, W, 2).cpu().numpy()
+        assert np.isfinite(to_np(want["result"])).all()
+        for r, d in enumerate(tiles):
+            assert d.halo_status() == 0, (f, r)
+            rx, ry, rw, rh = d.region
+            x, y, w, h = grid.tile(r)
+            for k, v in want.items():
+                t = torch.empty(3 * rw * rh, device="cuda")
+                got = (d.copy_output(t) if k == "result" else d.copy_state(k, t)).view(rh, rw, 3)
+                a = got[y - ry:y - ry + h, x - rx:x - rx + w].contiguous().view(torch.int32)
+                b = v[y:y + h, x:x + w].contiguous().view(torch.int32)
+                assert torch.equal(a, b), (f, r, k, int((a != b).sum()))
+            if f > 0:  # pixels of this tile whose reprojection lands in the image, in the other tile
+                q = pp[y:y + h, x:x + w]
+                inside = (q[..., 0] >= 0) & (q[..., 0] < W) & (q[..., 1] >= 0) & (q[..., 1] < H)
+                own = (q[..., 0] >= x) & (q[..., 0] < x + w) & (q[..., 1] >= y) & (q[..., 1] < y + h)
+                crossed[r] = crossed[r] or bool((inside & ~own).any())
+    if scene == "pan":
+        assert all(crossed), crossed
