@@ -74,7 +74,8 @@ class Sizes(C.Structure):
 
 class FrameInputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
-                ("noisy", "normals", "positions", "albedo", "prev_normals", "prev_positions")]
+                ("noisy", "normals", "positions", "albedo", "prev_normals", "prev_positions",
+                 "prev_pixel")]  # prev_pixel: optional float2 plane (include/bmfr.h), None = project
 
 
 class StateView(C.Structure):

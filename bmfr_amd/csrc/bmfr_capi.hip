@@ -565,6 +565,9 @@ bmfr::FusedArgs frame_args(const bmfr_ctx* c, const bmfr_frame_inputs* in, const
     A.done = nullptr;  // set per launch (one_launch_args)
     A.epoch = 0;
     A.sync_err = const_cast<unsigned*>(c->sync_host);
+    // The caller's previous-frame pixel plane replaces the projection from
+    // frame 1 on (frame 0 has no previous frame: ignored, like prev_normals).
+    A.prev_pixel_in = frame_number > 0 ? reinterpret_cast<const float2*>(in->prev_pixel) : nullptr;
     return A;
 }
 
@@ -836,7 +839,15 @@ bmfr_status bmfr_process_sequence(bmfr_ctx* c, void* stream, int count, const bm
                 ++c->prof_count;
             }
             if (ev) (void)hipEventRecord(ev[0], s);
-            e = bmfr::launch_fused_k1_taa(P, s, i < count ? &A : nullptr, prevP, pending ? &prevA : nullptr);
+            if (i < count && A.prev_pixel_in) {
+                // A frame that carries a prev_pixel plane: K2 of frame f - 1
+                // alone, then the plane-reading K1 alone (the same kernels'
+                // arithmetic, so the results are the one-launch form's).
+                e = pending ? bmfr::launch_fused_k1_taa(P, s, nullptr, prevP, &prevA) : hipSuccess;
+                if (e == hipSuccess) e = bmfr::launch_fused_k1_blocks(P, s, A);
+            } else {
+                e = bmfr::launch_fused_k1_taa(P, s, i < count ? &A : nullptr, prevP, pending ? &prevA : nullptr);
+            }
             if (ev) {  // K1 of f and K2 of f - 1 share the launch: all of it is reported as K1
                 (void)hipEventRecord(ev[1], s);
                 (void)hipEventRecord(ev[2], s);

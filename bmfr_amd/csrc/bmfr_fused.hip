@@ -305,7 +305,8 @@ __device__ __forceinline__ void back_substitute(K1Lds<B>& L, int t) {
 // accumulated colour and reprojected positions they read are stored
 // device-coherent and the block publishes done[...] = epoch once they are
 // (the hand-off of bmfr_taa_tile.h wait_k1_blocks).
-template <int NS, int FS, class IN, bool COH = false, bool FAST = false>
+// PLANE: the previous-frame pixel positions come from A.prev_pixel_in.
+template <int NS, int FS, class IN, bool COH = false, bool FAST = false, bool PLANE = false>
 __device__ __forceinline__ void k1_rows_body(const Params& P, const K1Args& A, K1Lds<NS + FS + 3>& L, int g) {
     constexpr int B = NS + FS + 3;
     const int t = threadIdx.x;
@@ -333,15 +334,16 @@ __device__ __forceinline__ void k1_rows_body(const Params& P, const K1Args& A, K
     int over = 0;
     uint32_t state = 0;  // per s: owner (bit 0), accept bits (1-4), spp (8-15) -> 16 bits each ...
     uint32_t state_hi = 0;
-    NoisyCur<IN> cur[kSubs];  // current-frame loads of all four rows go out first
+    NoisyCur<IN, PLANE> cur[kSubs];  // current-frame loads of all four rows go out first
 #pragma unroll
     for (int s = 0; s < kSubs; ++s)
-        cur[s] = noisy_load_current<IN>(P, in, bx * kEdge + (t & (kEdge - 1)), by * kEdge + (t >> 5) + 8 * s, frame);
+        cur[s] = noisy_load_current<IN, true, PLANE>(P, in, bx * kEdge + (t & (kEdge - 1)), by * kEdge + (t >> 5) + 8 * s,
+                                                     frame, A.prev_pixel_in);
 #pragma unroll
     for (int s = 0; s < kSubs; ++s) {
         // with accumulate_filtered_data's taps (FILT): the same taps and
         // weights, so phase 3 needs no second gather
-        const NoisyItem it = noisy_item_spec<true, IN>(P, in, A.cam, cur[s], frame, A.acc_prev);
+        const NoisyItem it = noisy_item_spec<true, IN, PLANE>(P, in, A.cam, cur[s], frame, A.acc_prev);
         L.keep[(s * 3 + 0) * kThreads + t] = it.prev_f.x;
         L.keep[(s * 3 + 1) * kThreads + t] = it.prev_f.y;
         L.keep[(s * 3 + 2) * kThreads + t] = it.prev_f.z;
@@ -483,33 +485,49 @@ __device__ __forceinline__ void k1_rows_body(const Params& P, const K1Args& A, K
 // Minimum waves per SIMD for the register allocator at B = 13: four (128
 // VGPRs, 12-32 bytes of spills) instead of three (129-130 VGPRs).
 constexpr int kRowsMinWaves = 4;
-template <int NS, int FS, class IN, bool FAST = false>
+template <int NS, int FS, class IN, bool FAST = false, bool PLANE = false>
 __global__ __launch_bounds__(kThreads, FS == 6 ? kRowsMinWaves : 3) void k_fused(Params P, K1Args A) {
     __shared__ K1Lds<NS + FS + 3> L;
-    k1_rows_body<NS, FS, IN, false, FAST>(P, A, L, xcd_swizzle(blockIdx.x, gridDim.x));
+    k1_rows_body<NS, FS, IN, false, FAST, PLANE>(P, A, L, xcd_swizzle(blockIdx.x, gridDim.x));
 }
 
 // The one-launch frame with this K1 (f32 tmp_data): K1 blocks, then the
 // frame's TAA tiles waiting on their completion flags (as k_fused_cols_taa,
 // bmfr_fused_cols.hip).
 static_assert(kThreads == kTileThreads, "the TAA tiles run on this kernel's work-groups");
-template <int NS, int FS, class IN, bool FAST = false>
+template <int NS, int FS, class IN, bool FAST = false, bool PLANE = false>
 __global__ __launch_bounds__(kThreads, FS == 6 ? kRowsMinWaves : 3) void k_fused_rows_taa(Params P, K1Args A, TaaArgs T, int nk1, int nk1p) {
     __shared__ union {
         K1Lds<NS + FS + 3> k1;
         FrameTaaLds k2;
     } U;
     const int b = blockIdx.x;
-    if (b < nk1) k1_rows_body<NS, FS, IN, true, FAST>(P, A, U.k1, xcd_swizzle(b, nk1));
+    if (b < nk1) k1_rows_body<NS, FS, IN, true, FAST, PLANE>(P, A, U.k1, xcd_swizzle(b, nk1));
     else if (b >= nk1p) frame_taa_part<IN, true>(P, T, b, nk1p, U.k2);
 }
 
+// This file is compiled twice: as it stands (the projecting kernels and the
+// public launchers) and from bmfr_fused_plane.hip with BMFR_ROWS_PLANE = 1
+// (the kernels reading bmfr_frame_inputs.prev_pixel; launchers *_plane).
+#ifndef BMFR_ROWS_PLANE
+#define BMFR_ROWS_PLANE 0
+#endif
+constexpr bool kRowsPlane = BMFR_ROWS_PLANE;
+hipError_t launch_fused_rows_frame_one_plane(const Params& P, hipStream_t st, const FusedArgs& A);
+hipError_t launch_fused_k1_plane(const Params& P, hipStream_t st, const FusedArgs& A);
+
+#if !BMFR_ROWS_PLANE
 bool fused_supported(const Params& P) {
     if (P.not_scaled != 4 || (P.scaled != 6 && P.scaled != 9)) return false;
     for (int f = 0; f < P.buffers - 3; ++f)
         if (P.codes[f] != f) return false;
     return true;
 }
+#endif
+
+// The launchers below differ between the two translation units under the same
+// names: internal linkage.
+namespace {
 
 // The row-split kernels' template arguments from the run-time parameters
 // (FS, the input element type, fast_fit), as dispatch_cols in bmfr_fused_cols.hip.
@@ -527,7 +545,7 @@ static void dispatch_rows(const Params& Q, Args&&... args) {
 template <int FS, class IN, bool FAST>
 struct LaunchK1 {
     static void go(const Params& P, hipStream_t st, const FusedArgs& A) {
-        hipLaunchKernelGGL((k_fused<4, FS, IN, FAST>), dim3(k1_blocks(P)), dim3(kThreads), 0, st, P, k1_args(A));
+        hipLaunchKernelGGL((k_fused<4, FS, IN, FAST, kRowsPlane>), dim3(k1_blocks(P)), dim3(kThreads), 0, st, P, k1_args(A));
     }
 };
 
@@ -535,19 +553,35 @@ template <int FS, class IN, bool FAST>
 struct LaunchRowsFrame {
     static void go(const Params& P, hipStream_t st, const FusedArgs& A) {
         const int nk1 = P.ring < 0 || P.nbx <= 0 || P.nby <= 0 ? 0 : k1_blocks(P), nk1p = (nk1 + 7) & ~7;
-        hipLaunchKernelGGL((k_fused_rows_taa<4, FS, IN, FAST>), dim3(nk1p + frame_taa_tiles(P)),
+        hipLaunchKernelGGL((k_fused_rows_taa<4, FS, IN, FAST, kRowsPlane>), dim3(nk1p + frame_taa_tiles(P)),
                            dim3(kThreads), 0, st, P, k1_args(A), taa_args(A), nk1, nk1p);
     }
 };
 
+}  // namespace
+
+#if BMFR_ROWS_PLANE
+hipError_t launch_fused_rows_frame_one_plane(const Params& P, hipStream_t st, const FusedArgs& A) {
+    dispatch_rows<LaunchRowsFrame>(P, P, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_fused_k1_plane(const Params& P, hipStream_t st, const FusedArgs& A) {
+    dispatch_rows<LaunchK1>(P, P, st, A);
+    return hipGetLastError();
+}
+#else
 hipError_t launch_fused_rows_frame_one(const Params& P, hipStream_t st, const FusedArgs& A) {
+    if (A.prev_pixel_in) return launch_fused_rows_frame_one_plane(P, st, A);
     dispatch_rows<LaunchRowsFrame>(P, P, st, A);
     return hipGetLastError();
 }
 
 hipError_t launch_fused_k1(const Params& P, hipStream_t st, const FusedArgs& A) {
+    if (A.prev_pixel_in) return launch_fused_k1_plane(P, st, A);
     dispatch_rows<LaunchK1>(P, P, st, A);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace bmfr

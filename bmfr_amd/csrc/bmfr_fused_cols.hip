@@ -851,7 +851,8 @@ __device__ __forceinline__ void back_substitute_regs(LDS& L, int t) {
 // COH: the TAA tiles of the same frame run in this launch: the accumulated
 // colour and the reprojected positions they read are stored device-coherent
 // and the block publishes done[g] = epoch once they are.
-template <int NS, int FS, class IN, bool COH = false, bool FAST = false, bool F32 = false>
+// PLANE: the previous-frame pixel positions come from A.prev_pixel_in.
+template <int NS, int FS, class IN, bool COH = false, bool FAST = false, bool F32 = false, bool PLANE = false>
 __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, Lds<NS + FS + 3, F32>& L, int g) {
     constexpr int B = NS + FS + 3;
     constexpr bool FASTR = FAST && !F32;  // WaveFit::FASTR
@@ -917,14 +918,17 @@ __device__ __forceinline__ void k1_cols_body(const Params& P, const K1Args& A, L
     // (three registers per item) spill 7 dwords and tie.
     constexpr bool kKeepNP = FAST && !F32 && B < 16;
     KeptNP<IN> keep_np[NI];
-    NoisyCur<IN> cur = noisy_load_current<IN>(P, A.in, bx * kEdge + lx, by * kEdge + item_row(l, 0), frame);
+    NoisyCur<IN, PLANE> cur = noisy_load_current<IN, true, PLANE>(P, A.in, bx * kEdge + lx, by * kEdge + item_row(l, 0), frame,
+                                                           A.prev_pixel_in);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        const NoisyTaps<IN> tp = noisy_taps_issue<true, IN>(P, A.in, A.cam, cur, frame, A.acc_prev);
-        NoisyCur<IN> nxt;
-        if (i < NI - 1) nxt = noisy_load_current<IN>(P, A.in, bx * kEdge + lx, by * kEdge + item_row(l, i + 1), frame);
+        const NoisyTaps<IN> tp = noisy_taps_issue<true, IN, PLANE>(P, A.in, A.cam, cur, frame, A.acc_prev);
+        NoisyCur<IN, PLANE> nxt;
+        if (i < NI - 1)
+            nxt = noisy_load_current<IN, true, PLANE>(P, A.in, bx * kEdge + lx, by * kEdge + item_row(l, i + 1), frame,
+                                                      A.prev_pixel_in);
         __builtin_amdgcn_sched_barrier(0);
-        const NoisyItem it = noisy_taps_finish<true, IN>(P, cur, tp, frame);
+        const NoisyItem it = noisy_taps_finish<true, IN, PLANE>(P, cur, tp, frame);
         if constexpr (kKeepNP) keep_np[i].set(cur.nrm, cur.wp);
         {
 #pragma unroll
@@ -1140,10 +1144,10 @@ constexpr int min_waves() {
 }
 
 // FAST: bmfr_config.fast_fit (the fused trailing update, update_column).
-template <int NS, int FS, class IN, bool FAST = false, bool F32 = false>
+template <int NS, int FS, class IN, bool FAST = false, bool F32 = false, bool PLANE = false>
 __global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32>())) void k_fused_cols(Params P, K1Args A) {
     __shared__ Lds<NS + FS + 3, F32> L;
-    k1_cols_body<NS, FS, IN, false, FAST, F32>(P, A, L, xcd_swizzle(blockIdx.x, gridDim.x));
+    k1_cols_body<NS, FS, IN, false, FAST, F32, PLANE>(P, A, L, xcd_swizzle(blockIdx.x, gridDim.x));
 }
 
 // K1 and K2 (64 x kFrameTaaH tiles) in one launch: work-groups [0, nk1) are K1
@@ -1159,7 +1163,7 @@ __global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32>())) void k_fused_co
 //     their outputs device-coherent.  Work-groups of one XCD are dispatched
 //     in order, so every K1 block a waiting tile needs has been dispatched:
 //     the waits end.
-template <int NS, int FS, class IN, bool SAME = false, bool FAST = false, bool F32 = false>
+template <int NS, int FS, class IN, bool SAME = false, bool FAST = false, bool F32 = false, bool PLANE = false>
 __global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32>())) void k_fused_cols_taa(Params P, K1Args A, Params P2,
                                                                                     TaaArgs T, int nk1, int nk1p) {
     __shared__ union {
@@ -1167,18 +1171,21 @@ __global__ __launch_bounds__(kK1Threads, (min_waves<FS, F32>())) void k_fused_co
         FrameTaaLds k2;
     } U;
     const int b = blockIdx.x;
-    if (b < nk1) k1_cols_body<NS, FS, IN, SAME, FAST, F32>(P, A, U.k1, xcd_swizzle(b, nk1));
+    if (b < nk1) k1_cols_body<NS, FS, IN, SAME, FAST, F32, PLANE>(P, A, U.k1, xcd_swizzle(b, nk1));
     else if (b >= nk1p) frame_taa_part<IN, SAME>(P2, T, b, nk1p, U.k2);
 }
 
 }  // namespace cols
 
-// The column-split kernels of one tmp_data precision, compiled in their own
-// translation unit (bmfr_fused_cols_f32.hip includes this file with
-// BMFR_COLS_F32 = 1): K1 alone, the one-launch frame, the sequence launch.
-template <bool F32>
+// The column-split kernels of one tmp_data precision and one source of the
+// previous-frame pixel positions, compiled in their own translation unit
+// (bmfr_fused_cols_f32.hip includes this file with BMFR_COLS_F32 = 1, the
+// *_plane.hip units with BMFR_COLS_PLANE = 1): K1 alone, the one-launch
+// frame, the sequence launch (projection only: a sequence frame that carries
+// a plane runs K1 alone, bmfr_process_sequence).
+template <bool F32, bool PLANE>
 hipError_t launch_cols_k1(const Params& P, hipStream_t st, const FusedArgs& A);
-template <bool F32>
+template <bool F32, bool PLANE>
 hipError_t launch_cols_frame_one(const Params& P, hipStream_t st, const FusedArgs& A);
 template <bool F32>
 hipError_t launch_cols_k1_taa(const Params& P, hipStream_t st, const FusedArgs* A, const Params& P2,
@@ -1187,9 +1194,13 @@ hipError_t launch_cols_k1_taa(const Params& P, hipStream_t st, const FusedArgs* 
 #ifndef BMFR_COLS_F32
 #define BMFR_COLS_F32 0
 #endif
+#ifndef BMFR_COLS_PLANE
+#define BMFR_COLS_PLANE 0
+#endif
 constexpr bool kColsF32 = BMFR_COLS_F32;
+constexpr bool kColsPlane = BMFR_COLS_PLANE;
 
-// The launchers below differ between the two translation units (kColsF32)
+// The launchers below differ between the translation units (kColsF32, kColsPlane)
 // under the same names: internal linkage, or the linker keeps one TU's copy
 // of each inline go() for both.
 namespace {
@@ -1225,7 +1236,7 @@ bool dispatch_cols(const Params& Q, Args&&... args) {
 template <int FS, class IN, bool FAST>
 struct LaunchCols {
     static void go(const Params& P, hipStream_t st, const FusedArgs& A) {
-        hipLaunchKernelGGL((cols::k_fused_cols<4, FS, IN, FAST, kColsF32>), dim3(k1_blocks(P)),
+        hipLaunchKernelGGL((cols::k_fused_cols<4, FS, IN, FAST, kColsF32, kColsPlane>), dim3(k1_blocks(P)),
                            dim3(cols::kK1Threads), 0, st, P, k1_args(A));
     }
 };
@@ -1235,11 +1246,12 @@ struct LaunchFrameOne {
     static void go(const Params& P, hipStream_t st, const FusedArgs& A) {
         const int nk1 = P.ring < 0 || P.nbx <= 0 || P.nby <= 0 ? 0 : k1_blocks(P), nk1p = (nk1 + 7) & ~7;
         const int nk2 = frame_taa_tiles(P);
-        hipLaunchKernelGGL((cols::k_fused_cols_taa<4, FS, IN, true, FAST, kColsF32>), dim3(nk1p + nk2),
+        hipLaunchKernelGGL((cols::k_fused_cols_taa<4, FS, IN, true, FAST, kColsF32, kColsPlane>), dim3(nk1p + nk2),
                            dim3(cols::kK1Threads), 0, st, P, k1_args(A), P, taa_args(A), nk1, nk1p);
     }
 };
 
+#if !BMFR_COLS_PLANE
 template <int FS, class IN, bool FAST>
 struct LaunchColsTaa {
     static void go(const Params& P, hipStream_t st, const FusedArgs* A, const Params& P2, const FusedArgs* A2) {
@@ -1252,27 +1264,44 @@ struct LaunchColsTaa {
                            nk1p);
     }
 };
+#endif
 
 }  // namespace
 
 template <>
-hipError_t launch_cols_k1<kColsF32>(const Params& P, hipStream_t st, const FusedArgs& A) {
+hipError_t launch_cols_k1<kColsF32, kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A) {
     if (!dispatch_cols<LaunchCols>(P, P, st, A)) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 template <>
-hipError_t launch_cols_frame_one<kColsF32>(const Params& P, hipStream_t st, const FusedArgs& A) {
+hipError_t launch_cols_frame_one<kColsF32, kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A) {
     if (!dispatch_cols<LaunchFrameOne>(P, P, st, A)) return hipErrorInvalidValue;
     return hipGetLastError();
 }
+#if !BMFR_COLS_PLANE
 template <>
 hipError_t launch_cols_k1_taa<kColsF32>(const Params& P, hipStream_t st, const FusedArgs* A, const Params& P2,
                                         const FusedArgs* A2) {
     if (!dispatch_cols<LaunchColsTaa>(A ? P : P2, P, st, A, P2, A2)) return hipErrorInvalidValue;
     return hipGetLastError();
 }
+#endif
 
-#if !BMFR_COLS_F32
+// The other units' launchers.
+template <>
+hipError_t launch_cols_k1<!kColsF32, kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A);
+template <>
+hipError_t launch_cols_k1<kColsF32, !kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A);
+template <>
+hipError_t launch_cols_k1<!kColsF32, !kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A);
+template <>
+hipError_t launch_cols_frame_one<!kColsF32, kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A);
+template <>
+hipError_t launch_cols_frame_one<kColsF32, !kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A);
+template <>
+hipError_t launch_cols_frame_one<!kColsF32, !kColsPlane>(const Params& P, hipStream_t st, const FusedArgs& A);
+
+#if !BMFR_COLS_F32 && !BMFR_COLS_PLANE
 // f32 tmp_data with fast_fit runs the column-split K1 too
 // (bmfr_fused_cols_f32.hip); its exact fit is the row-split K1 of bmfr_fused.hip.
 bool fused_cols_supported(const Params& P) { return (P.half_tmp || P.fast_fit) && fused_supported(P); }
@@ -1285,7 +1314,9 @@ bool frame_fused_supported(const Params& P) { return fused_supported(P); }
 
 hipError_t launch_fused_frame_one(const Params& P, hipStream_t st, const FusedArgs& A) {
     if (!fused_cols_supported(P)) return launch_fused_rows_frame_one(P, st, A);  // f32 tmp_data, exact fit
-    return P.half_tmp ? launch_cols_frame_one<false>(P, st, A) : launch_cols_frame_one<true>(P, st, A);
+    if (A.prev_pixel_in)
+        return P.half_tmp ? launch_cols_frame_one<false, true>(P, st, A) : launch_cols_frame_one<true, true>(P, st, A);
+    return P.half_tmp ? launch_cols_frame_one<false, false>(P, st, A) : launch_cols_frame_one<true, false>(P, st, A);
 }
 
 hipError_t launch_fused_k1_taa(const Params& P, hipStream_t st, const FusedArgs* A, const Params& P2,
@@ -1295,7 +1326,8 @@ hipError_t launch_fused_k1_taa(const Params& P, hipStream_t st, const FusedArgs*
 }
 
 hipError_t launch_fused_k1_cols(const Params& P, hipStream_t st, const FusedArgs& A) {
-    return P.half_tmp ? launch_cols_k1<false>(P, st, A) : launch_cols_k1<true>(P, st, A);
+    if (A.prev_pixel_in) return P.half_tmp ? launch_cols_k1<false, true>(P, st, A) : launch_cols_k1<true, true>(P, st, A);
+    return P.half_tmp ? launch_cols_k1<false, false>(P, st, A) : launch_cols_k1<true, false>(P, st, A);
 }
 #endif
 

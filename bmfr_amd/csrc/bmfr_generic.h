@@ -68,7 +68,8 @@ __global__ __launch_bounds__(256) void k_fused_block(Params P, NoisyInputs in, C
                                                      uint8_t* __restrict__ spp_out,
                                                      float2* __restrict__ prev_pixel_out,
                                                      float* __restrict__ acc_out,
-                                                     float* __restrict__ tone_out) {
+                                                     float* __restrict__ tone_out,
+                                                     const float2* __restrict__ prev_pixel_in) {
     constexpr int B = NS + FS + 3;
     __shared__ FitLds<B> L;
     const int t = threadIdx.x, g = blockIdx.x;
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(256) void k_fused_block(Params P, NoisyInputs in, C
     for (int s = 0; s < kSubs; ++s) {
         const int r = t + s * kLocal;
         const int gx = bx * kEdge + (r & (kEdge - 1)), gy = by * kEdge + (r >> 5);
-        const NoisyItem it = noisy_item(P, in, cam, gx, gy, frame);
+        const NoisyItem it = noisy_item(P, in, cam, gx, gy, frame, prev_pixel_in);
 #pragma unroll
         for (int f = 0; f < B; ++f) {
             const float v = design_value(P, f, it);
@@ -134,11 +135,11 @@ static hipError_t launch_fused_t(const Params& P, hipStream_t st, const FusedArg
     if (P.half_tmp)
         hipLaunchKernelGGL((k_fused_block<NS, FS, true>), dim3(G), dim3(256), 0, st, P, A.in, A.cam,
                            A.frame, A.albedo, A.acc_prev, A.noisy_out, A.spp_out, A.prev_pixel_out,
-                           A.acc_out, A.tone_out);
+                           A.acc_out, A.tone_out, A.prev_pixel_in);
     else
         hipLaunchKernelGGL((k_fused_block<NS, FS, false>), dim3(G), dim3(256), 0, st, P, A.in, A.cam,
                            A.frame, A.albedo, A.acc_prev, A.noisy_out, A.spp_out, A.prev_pixel_out,
-                           A.acc_out, A.tone_out);
+                           A.acc_out, A.tone_out, A.prev_pixel_in);
     return hipGetLastError();
 }
 

@@ -162,8 +162,11 @@ __device__ __forceinline__ uint32_t pix(const Params& P, int x, int y) {
 __device__ __forceinline__ int clamp_rx(const Params& P, int x) { return min(max(x, P.ox), P.ox + P.stride - 1); }
 __device__ __forceinline__ int clamp_ry(const Params& P, int y) { return min(max(y, P.oy), P.oy + P.rows - 1); }
 
+// pf_plane (generic-feature K1 only, wave-uniform): the caller's previous-
+// frame pixel plane (bmfr_frame_inputs.prev_pixel) replaces the projection.
 __device__ __forceinline__ NoisyItem noisy_item(const Params& P, const NoisyInputs& in,
-                                                const Camera& cam, int gx, int gy, int frame) {
+                                                const Camera& cam, int gx, int gy, int frame,
+                                                const float2* __restrict__ pf_plane = nullptr) {
     NoisyItem o;
     const int2 off = kBlockOffsets[frame & 15];
     const int ux = gx - kEdge / 2 + off.x, uy = gy - kEdge / 2 + off.y;
@@ -183,22 +186,32 @@ __device__ __forceinline__ NoisyItem noisy_item(const Params& P, const NoisyInpu
     f3 prev{0.f, 0.f, 0.f};
     float sample_spp = 0.f;
     if (frame > 0) {
-        const float* M = cam.m;
-        // .s048c / .s159d / .s37bf rows of the column-major matrix (bmfr.cl:343-347)
-        float u = dot4(M[0], M[4], M[8], M[12], wp.x, wp.y, wp.z, 1.f);
-        float v = dot4(M[1], M[5], M[9], M[13], wp.x, wp.y, wp.z, 1.f);
-        const float w = dot4(M[3], M[7], M[11], M[15], wp.x, wp.y, wp.z, 1.f);
-        const float rw = 1.f / w;  // u / w and v / w share the divisor
-        u = div_shared(u, w, rw);
-        v = div_shared(v, w, rw);
-        u = u + 1.f;
-        v = v + 1.f;
-        u = u / 2.f;
-        v = v / 2.f;
-        pfx = u * (float)P.width - cam.jx;
-        pfy = v * (float)P.height - (1 - cam.jy);
+        if (pf_plane) {
+            const float2 pf = ld_px(pf_plane, o.lin);
+            pfx = pf.x;
+            pfy = pf.y;
+        } else {
+            const float* M = cam.m;
+            // .s048c / .s159d / .s37bf rows of the column-major matrix (bmfr.cl:343-347)
+            float u = dot4(M[0], M[4], M[8], M[12], wp.x, wp.y, wp.z, 1.f);
+            float v = dot4(M[1], M[5], M[9], M[13], wp.x, wp.y, wp.z, 1.f);
+            const float w = dot4(M[3], M[7], M[11], M[15], wp.x, wp.y, wp.z, 1.f);
+            const float rw = 1.f / w;  // u / w and v / w share the divisor
+            u = div_shared(u, w, rw);
+            v = div_shared(v, w, rw);
+            u = u + 1.f;
+            v = v + 1.f;
+            u = u / 2.f;
+            v = v / 2.f;
+            pfx = u * (float)P.width - cam.jx;
+            pfy = v * (float)P.height - (1 - cam.jy);
+        }
         const float flx = floorf(pfx), fly = floorf(pfy);
-        const int ix = (int)flx, iy = (int)fly;
+        // A plane entry may be any float (far off, infinite, NaN): clamped in
+        // float as reproject_taps does, so every such tap lies outside the
+        // image (the identity for a tap inside it).
+        const int ix = pf_plane ? (int)fminf(fmaxf(flx, -2.f), (float)P.width + 1.f) : (int)flx;
+        const int iy = pf_plane ? (int)fminf(fmaxf(fly, -2.f), (float)P.height + 1.f) : (int)fly;
         const float fx = pfx - flx, fy = pfy - fly;
         const float omx = 1.f - fx, omy = 1.f - fy;
         const float wts[4] = {omx * omy, fx * omy, omx * fy, fx * fy};
@@ -253,8 +266,16 @@ __device__ __forceinline__ NoisyItem noisy_item(const Params& P, const NoisyInpu
 // ignored), so a pixel costs two dependent memory round trips instead of up
 // to four.  The arithmetic, its order and the results are noisy_item's.
 // The current-frame planes of one item, as loaded (widened where used).
-template <class IN = float>
-struct NoisyCur {
+// PLANE (the previous-frame pixel position comes from the caller's plane, not
+// the projection) adds that position; without it the struct is as it was.
+template <bool PLANE>
+struct NoisyCurPf {};
+template <>
+struct NoisyCurPf<true> {
+    float2 pf;
+};
+template <class IN = float, bool PLANE = false>
+struct NoisyCur : NoisyCurPf<PLANE> {
     In3<IN> wp, nrm, cur;
     int px, py;
     bool owner;
@@ -270,15 +291,21 @@ __device__ __forceinline__ void item_pixel(const Params& P, int gx, int gy, int 
     owner = ux >= 0 && ux < P.width && uy >= 0 && uy < P.height;
 }
 
-template <class IN = float, bool COLOUR = true>
-__device__ __forceinline__ NoisyCur<IN> noisy_load_current(const Params& P, const NoisyInputs& in, int gx, int gy,
-                                                           int frame) {
-    NoisyCur<IN> c;
+// PLANE: the previous-frame pixel position comes from the caller's plane
+// pf_plane (bmfr_frame_inputs.prev_pixel: float2 per pixel of the region,
+// always f32) instead of the projection -- one 8-byte load at the item's
+// (mirrored) pixel, issued with the other current-frame loads.
+template <class IN = float, bool COLOUR = true, bool PLANE = false>
+__device__ __forceinline__ NoisyCur<IN, PLANE> noisy_load_current(const Params& P, const NoisyInputs& in, int gx,
+                                                                  int gy, int frame,
+                                                                  const float2* __restrict__ pf_plane = nullptr) {
+    NoisyCur<IN, PLANE> c;
     item_pixel(P, gx, gy, frame, c.px, c.py, c.owner);
     const uint32_t lin = pix(P, c.px, c.py);
     c.wp = ld3raw<IN>(in.p_cur, lin);
     c.nrm = ld3raw<IN>(in.n_cur, lin);
     if constexpr (COLOUR) c.cur = ld3raw<IN>(in.noisy_cur, lin);
+    if constexpr (PLANE) c.pf = ld_px(pf_plane, lin);
     return c;
 }
 
@@ -334,8 +361,10 @@ struct Reproj {
     uint32_t inb;
     int over;
 };
-__device__ __forceinline__ Reproj reproject(const Params& P, const Camera& cam, const f3& wp, int px, int py) {
-    Reproj r;
+// The projection (bmfr.cl:343-358): world position wp through the previous
+// frame's view-projection matrix to the previous-frame pixel position pf
+// (pfx = u W - jx, pfy = v H - (1 - jy); integers are pixel indices).
+__device__ __forceinline__ void project_prev(const Params& P, const Camera& cam, const f3& wp, float& pfx, float& pfy) {
     const float* M = cam.m;
     float u = dot4(M[0], M[4], M[8], M[12], wp.x, wp.y, wp.z, 1.f);
     float v = dot4(M[1], M[5], M[9], M[13], wp.x, wp.y, wp.z, 1.f);
@@ -347,8 +376,14 @@ __device__ __forceinline__ Reproj reproject(const Params& P, const Camera& cam, 
     v = v + 1.f;
     u = u / 2.f;
     v = v / 2.f;
-    const float pfx = u * (float)P.width - cam.jx;
-    const float pfy = v * (float)P.height - (1 - cam.jy);
+    pfx = u * (float)P.width - cam.jx;
+    pfy = v * (float)P.height - (1 - cam.jy);
+}
+// The rest (bmfr.cl:359-372): from pf -- projected, or read from the caller's
+// plane, where it may be any float: far off, infinite or NaN all clamp to a
+// tap position outside the image -- to the taps, weights, inb and over.
+__device__ __forceinline__ Reproj reproject_taps(const Params& P, float pfx, float pfy, int px, int py) {
+    Reproj r;
     r.pfx = pfx;
     r.pfy = pfy;
     const float flx = floorf(pfx), fly = floorf(pfy);
@@ -376,10 +411,15 @@ __device__ __forceinline__ Reproj reproject(const Params& P, const Camera& cam, 
     }
     return r;
 }
+__device__ __forceinline__ Reproj reproject(const Params& P, const Camera& cam, const f3& wp, int px, int py) {
+    float pfx, pfy;
+    project_prev(P, cam, wp, pfx, pfy);
+    return reproject_taps(P, pfx, pfy, px, py);
+}
 
-template <bool FILT = false, class IN = float>
+template <bool FILT = false, class IN = float, bool PLANE = false>
 __device__ __forceinline__ NoisyTaps<IN> noisy_taps_issue(const Params& P, const NoisyInputs& in, const Camera& cam,
-                                                         const NoisyCur<IN>& c, int frame,
+                                                         const NoisyCur<IN, PLANE>& c, int frame,
                                                          const float* __restrict__ acc_prev = nullptr) {
     NoisyTaps<IN> tp;
     tp.pfx = (float)c.px;
@@ -387,7 +427,9 @@ __device__ __forceinline__ NoisyTaps<IN> noisy_taps_issue(const Params& P, const
     tp.over = 0;
     tp.inb = 0;
     if (frame > 0) {
-        const Reproj r = reproject(P, cam, widen(c.wp), c.px, c.py);
+        Reproj r;
+        if constexpr (PLANE) r = reproject_taps(P, c.pf.x, c.pf.y, c.px, c.py);
+        else r = reproject(P, cam, widen(c.wp), c.px, c.py);
         tp.pfx = r.pfx;
         tp.pfy = r.pfy;
         tp.over = r.over;
@@ -545,8 +587,8 @@ __device__ __forceinline__ void split_pairs(const h3pair (&q)[2], uint32_t fix, 
     }
 }
 
-template <bool FILT = false, class IN = float>
-__device__ __forceinline__ NoisyItem noisy_taps_finish(const Params& P, const NoisyCur<IN>& c,
+template <bool FILT = false, class IN = float, bool PLANE = false>
+__device__ __forceinline__ NoisyItem noisy_taps_finish(const Params& P, const NoisyCur<IN, PLANE>& c,
                                                       const NoisyTaps<IN>& tp, int frame) {
     const f3 wp = widen(c.wp), nrm = widen(c.nrm), cur = widen(c.cur);
     uint32_t accept = 0u;
@@ -567,11 +609,11 @@ __device__ __forceinline__ NoisyItem noisy_taps_finish(const Params& P, const No
     return o;
 }
 
-template <bool FILT = false, class IN = float>
+template <bool FILT = false, class IN = float, bool PLANE = false>
 __device__ __forceinline__ NoisyItem noisy_item_spec(const Params& P, const NoisyInputs& in, const Camera& cam,
-                                                     const NoisyCur<IN>& c, int frame,
+                                                     const NoisyCur<IN, PLANE>& c, int frame,
                                                      const float* __restrict__ acc_prev = nullptr) {
-    return noisy_taps_finish<FILT, IN>(P, c, noisy_taps_issue<FILT, IN>(P, in, cam, c, frame, acc_prev), frame);
+    return noisy_taps_finish<FILT, IN, PLANE>(P, c, noisy_taps_issue<FILT, IN, PLANE>(P, in, cam, c, frame, acc_prev), frame);
 }
 
 // One work-group's reprojection-reach report (tiled contexts): the lanes

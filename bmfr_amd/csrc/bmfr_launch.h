@@ -43,6 +43,9 @@ struct FusedArgs {
     unsigned* done;       // one-launch frame: per K1 block, the epoch of the launch that completed it
     unsigned epoch;       // this launch's epoch (context-wide launch counter, never 0)
     unsigned* sync_err;   // page-locked report of an exhausted wait (kSyncPivot / kSyncTile), or null
+    // bmfr_frame_inputs.prev_pixel from frame 1 on (null: project with cam): the
+    // caller's previous-frame pixel position of every region pixel
+    const float2* prev_pixel_in;
 };
 
 // Kernel arguments of the fused K1 (canonical feature lists).
@@ -61,10 +64,11 @@ struct K1Args {
     unsigned* done;
     unsigned epoch;
     unsigned* sync_err;
+    const float2* prev_pixel_in;  // read by the PLANE kernels only (last: the others' argument layout is unchanged)
 };
 inline K1Args k1_args(const FusedArgs& A) {
-    return K1Args{A.in,      A.cam,         A.frame, A.acc_prev, A.noisy_out, A.spp_out, A.prev_pixel_out,
-                  A.acc_out, A.noise_table, A.reach, A.stamps,   A.done,      A.epoch,   A.sync_err};
+    return K1Args{A.in,      A.cam,         A.frame, A.acc_prev, A.noisy_out, A.spp_out,  A.prev_pixel_out, A.acc_out,
+                  A.noise_table, A.reach,   A.stamps, A.done,    A.epoch,     A.sync_err, A.prev_pixel_in};
 }
 inline TaaArgs taa_args(const FusedArgs& A) {
     return TaaArgs{A.acc_out, A.albedo, A.prev_pixel_out, A.result_out, A.result_prev, A.frame, A.reach,
@@ -81,6 +85,11 @@ bool fused_supported(const Params& P);
 // The canonical path tone-maps in K2 (bmfr.cl:851-856), for each tile pixel
 // and its 1-px halo.  f32 tmp_data: row-split K1 (bmfr_fused.hip).
 hipError_t launch_fused_k1(const Params& P, hipStream_t st, const FusedArgs& A);
+// The launchers of the fused K1s pick the PLANE kernels -- the same kernels
+// with the previous-frame pixel position read from A.prev_pixel_in instead of
+// projected, compiled in translation units of their own (bmfr_fused_plane.hip,
+// bmfr_fused_cols_plane.hip, bmfr_fused_cols_f32_plane.hip) -- when that
+// plane is set.
 // Column-split K1 (bmfr_fused_cols.hip): half tmp_data.
 bool fused_cols_supported(const Params& P);
 hipError_t launch_fused_k1_cols(const Params& P, hipStream_t st, const FusedArgs& A);

@@ -96,6 +96,28 @@ def _ptr(t) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def check_prev_pixel(plane, width: int, height: int, device: int = 0) -> None:
+    """Raise unless `plane` can be passed as bmfr_frame_inputs.prev_pixel
+    (include/bmfr.h) of a context whose planes cover width x height pixels (the
+    image, or a tiled context's region) on GPU `device`: a contiguous float32
+    tensor of shape (height, width, 2) or (height * width * 2,) there.  None
+    (project with the camera matrix) passes.  Runs before any library call,
+    which would read a wrong plane out of bounds."""
+    if plane is None:
+        return
+    if not isinstance(plane, torch.Tensor):
+        raise TypeError(f"prev_pixel must be a torch tensor or None, not {type(plane).__name__}")
+    if plane.dtype != torch.float32:
+        raise TypeError(f"prev_pixel must be float32 (also with input_half), not {plane.dtype}")
+    if tuple(plane.shape) not in ((height, width, 2), (height * width * 2,)):
+        raise ValueError(f"prev_pixel must have shape ({height}, {width}, 2) or ({height * width * 2},), "
+                         f"not {tuple(plane.shape)}")
+    if not plane.is_contiguous():
+        raise ValueError("prev_pixel must be contiguous")
+    if plane.device.type != "cuda" or (plane.device.index or 0) != device:
+        raise ValueError(f"prev_pixel must live on cuda:{device}, not {plane.device}")
+
+
 def _stream(stream) -> int | None:
     s = stream if stream is not None else torch.cuda.current_stream()
     return s.cuda_stream
@@ -205,38 +227,51 @@ class Denoiser(_Context):
         super().__init__(cfg, device)
         self.prev_inputs = None
 
+    def _check_prev_pixel(self, plane) -> None:
+        check_prev_pixel(plane, self.sizes.region_width, self.sizes.region_height, self.device)
+
     def _call(self, fn: str, noisy, normals, positions, albedo, prev_vp, jitter, frame, prev_normals,
-              prev_positions, stream, done: bool) -> None:
+              prev_positions, stream, done: bool, prev_pixel=None) -> None:
+        self._check_prev_pixel(prev_pixel)
         if frame > 0 and prev_normals is None:
             if self.prev_inputs is None:
                 raise ValueError("frame > 0 needs the previous frame's normals/positions")
             prev_normals, prev_positions = self.prev_inputs
         fi = _lib.FrameInputs(_ptr(noisy), _ptr(normals), _ptr(positions), _ptr(albedo),
-                              _ptr(prev_normals), _ptr(prev_positions))
+                              _ptr(prev_normals), _ptr(prev_positions), _ptr(prev_pixel))
         check(getattr(self.lib, fn)(self.handle, _stream(stream), C.byref(fi), floats(prev_vp, 16),
                                     floats(jitter, 2), frame), fn)
         if done:
             self.prev_inputs = (normals, positions)
 
     def process_frame(self, noisy, normals, positions, albedo, prev_vp, jitter, frame: int,
-                      prev_normals=None, prev_positions=None, stream=None) -> None:
+                      prev_normals=None, prev_positions=None, stream=None, prev_pixel=None) -> None:
         """Run one frame.  prev_normals / prev_positions default to the ones
-        passed on the previous call (the reference's Double_buffer halves)."""
+        passed on the previous call (the reference's Double_buffer halves).
+        prev_pixel: optional float32 (H, W, 2) plane of previous-frame pixel
+        positions that replaces the projection through prev_vp from frame 1 on
+        (include/bmfr.h bmfr_frame_inputs.prev_pixel; the region for a tile)."""
         self._call("bmfr_process_frame", noisy, normals, positions, albedo, prev_vp, jitter, frame,
-                   prev_normals, prev_positions, stream, True)
+                   prev_normals, prev_positions, stream, True, prev_pixel)
 
     def process_sequence(self, frames, cameras, first_frame: int, outputs=None, stream=None) -> None:
         """Frames first_frame .. first_frame+len(frames)-1 in one pipelined call
         (include/bmfr.h bmfr_process_sequence).  frames: dicts with noisy,
-        normals, positions, albedo tensors; cameras: (prev_vp, jitter) per
-        frame; outputs: optional tensors receiving each frame's output."""
+        normals, positions, albedo tensors and optionally prev_pixel (a plane
+        as in process_frame, or None) and prev_normals / prev_positions
+        (default: the frame before's normals / positions); cameras: (prev_vp,
+        jitter) per frame; outputs: optional tensors receiving each frame's
+        output."""
         n = len(frames)
         arr = (_lib.FrameInputs * n)()
         prev = self.prev_inputs
         for i, fr in enumerate(frames):
             pn, pp = prev if prev is not None else (None, None)
+            if fr.get("prev_normals") is not None:
+                pn, pp = fr["prev_normals"], fr["prev_positions"]
+            self._check_prev_pixel(fr.get("prev_pixel"))
             arr[i] = _lib.FrameInputs(_ptr(fr["noisy"]), _ptr(fr["normals"]), _ptr(fr["positions"]),
-                                      _ptr(fr["albedo"]), _ptr(pn), _ptr(pp))
+                                      _ptr(fr["albedo"]), _ptr(pn), _ptr(pp), _ptr(fr.get("prev_pixel")))
             prev = (fr["normals"], fr["positions"])
         vps = floats([v for vp, _ in cameras for v in vp], 16 * n)
         offs = floats([v for _, jit in cameras for v in jit], 2 * n)
@@ -248,17 +283,17 @@ class Denoiser(_Context):
         self.prev_inputs = prev
 
     def process_frame_interior(self, noisy, normals, positions, albedo, prev_vp, jitter, frame: int,
-                               prev_normals=None, prev_positions=None, stream=None) -> None:
+                               prev_normals=None, prev_positions=None, stream=None, prev_pixel=None) -> None:
         """First half of a frame (include/bmfr.h): the K1 blocks that need no
         halo; may run while the halo exchange of the previous state is in flight."""
         self._call("bmfr_process_frame_interior", noisy, normals, positions, albedo, prev_vp, jitter, frame,
-                   prev_normals, prev_positions, stream, False)
+                   prev_normals, prev_positions, stream, False, prev_pixel)
 
     def process_frame_border(self, noisy, normals, positions, albedo, prev_vp, jitter, frame: int,
-                             prev_normals=None, prev_positions=None, stream=None) -> None:
+                             prev_normals=None, prev_positions=None, stream=None, prev_pixel=None) -> None:
         """Second half: the remaining K1 blocks and K2, once the halo is refreshed."""
         self._call("bmfr_process_frame_border", noisy, normals, positions, albedo, prev_vp, jitter, frame,
-                   prev_normals, prev_positions, stream, True)
+                   prev_normals, prev_positions, stream, True, prev_pixel)
 
     def halo_status(self) -> int:
         """Tiled contexts: waits for the last frame; the largest distance (px)

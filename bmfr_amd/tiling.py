@@ -391,6 +391,45 @@ def halo_rects(region: Rect, tile: Rect) -> list:
     return [r for r in out if r[2] > 0 and r[3] > 0]
 
 
+def region_slice(plane, width: int, height: int, region: Rect):
+    """The pixels of `region` (x, y, w, h) of a full-frame plane (a tensor of
+    width * height pixels, any channel count) as a contiguous tensor with row
+    stride w: what a tiled context takes for that plane -- an input plane, or
+    the frame's prev_pixel plane (bmfr_frame_inputs.prev_pixel; its entries
+    are frame coordinates, so a slice needs no offset)."""
+    x, y, w, h = region
+    return plane.reshape(height, width, -1)[y:y + h, x:x + w].contiguous()
+
+
+def process_frame_tiled(denoisers, frame_planes, prev_vp, jitter, frame: int, exchange=None, prev_planes=None,
+                        prev_pixel=None) -> None:
+    """One frame on every rank of an in-process tile grid: full-frame planes
+    (dict of noisy / normals / positions / albedo tensors, `prev_planes` the
+    previous frame's) and the optional full-frame prev_pixel plane are cut to
+    each rank's region; from frame 1 on, `exchange(frame)` refreshes the halos
+    between the interior and the border halves of the frame."""
+    W, H = denoisers[0].cfg.image_width, denoisers[0].cfg.image_height
+    calls = []
+    for d in denoisers:
+        cut = lambda t: region_slice(t, W, H, d.region).reshape(-1)  # noqa: E731
+        args = [cut(frame_planes[k]) for k in ("noisy", "normals", "positions", "albedo")]
+        kw = {}
+        if frame > 0:
+            kw = dict(prev_normals=cut(prev_planes["normals"]), prev_positions=cut(prev_planes["positions"]),
+                      prev_pixel=None if prev_pixel is None else cut(prev_pixel))
+        calls.append((d, args + [prev_vp, jitter, frame], kw))
+    if frame == 0:
+        for d, a, kw in calls:
+            d.process_frame(*a, **kw)
+        return
+    for d, a, kw in calls:
+        d.process_frame_interior(*a, **kw)
+    if exchange is not None:
+        exchange(frame)
+    for d, a, kw in calls:
+        d.process_frame_border(*a, **kw)
+
+
 def state_planes(denoiser) -> list:
     """The four exchanged planes of a tiled Denoiser's last frame (the next frame's previous state)."""
     v = denoiser.state(previous=False)

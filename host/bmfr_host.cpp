@@ -73,6 +73,10 @@ struct Options {
     // with --gpus N = tiles, device copies when every tile is on one GPU)
     int tiles_x = 0, tiles_y = 0, tile_halo = 64, gpus = 1;
     int fast_fit = 0;
+    // --dump-prev-pixel / --prev-pixel PREFIX: each frame's previous-frame pixel
+    // plane (bmfr_state_view.prev_frame_pixel / bmfr_frame_inputs.prev_pixel)
+    // as PREFIXNN.exr, FLOAT, R = x, G = y, B = 0
+    std::string dump_prev_pixel, prev_pixel;
 };
 
 void usage() {
@@ -97,7 +101,11 @@ void usage() {
         "  --tile-halo PX         tile halo in pixels (default 64; >= 34 + the scene's motion per frame)\n"
         "  --gpus N               tiles on N GPUs from --device on (N = 1: all on one GPU, device copies;\n"
         "                         N = tiles: one GPU per tile, RCCL)\n"
-        "  --fast-fit             bmfr_config.fast_fit = 1\n");
+        "  --fast-fit             bmfr_config.fast_fit = 1\n"
+        "  --dump-prev-pixel PREFIX  write each frame's previous-frame pixel positions (the plane K1\n"
+        "                         stores) as PREFIXNN.exr: FLOAT, R = x, G = y, B = 0\n"
+        "  --prev-pixel PREFIX    read such files and pass them as bmfr_frame_inputs.prev_pixel from\n"
+        "                         frame 1 on, instead of projecting with the camera matrices\n");
 }
 
 bool parse_args(int argc, char** argv, Options& o) {
@@ -136,6 +144,8 @@ bool parse_args(int argc, char** argv, Options& o) {
         } else if (a == "--tile-halo") o.tile_halo = std::atoi(next("pixels"));
         else if (a == "--gpus") o.gpus = std::atoi(next("a count"));
         else if (a == "--fast-fit") o.fast_fit = 1;
+        else if (a == "--dump-prev-pixel") o.dump_prev_pixel = next("a prefix");
+        else if (a == "--prev-pixel") o.prev_pixel = next("a prefix");
         else if (a == "-h" || a == "--help") {
             usage();
             std::exit(0);
@@ -576,6 +586,24 @@ int run(const Options& o) {
         if (ctx) bmfr_destroy(ctx);
         return 1;
     }
+    if (tiled && (!o.dump_prev_pixel.empty() || !o.prev_pixel.empty())) {
+        std::fprintf(stderr, "--dump-prev-pixel / --prev-pixel are not available with --tile-grid\n");
+        return 1;
+    }
+    // ---- Previous-frame pixel planes (--prev-pixel): float2 per pixel from frame 1 on ----
+    const size_t px_count = (size_t)W * H;
+    std::vector<std::vector<float>> pp_in(o.prev_pixel.empty() ? 0 : F), pp_out(o.dump_prev_pixel.empty() ? 0 : F);
+    for (int f = 1; f < (int)pp_in.size(); ++f) {
+        std::vector<float> rgb(plane);
+        if (bmfr_exr_read_rgb(frame_file(o.prev_pixel, f, ".exr").c_str(), W, H, rgb.data()) != 0) {
+            std::printf("Buffer loading failed, reason: %s\n", bmfr_io_error());
+            if (ctx) bmfr_destroy(ctx);
+            return 1;
+        }
+        pp_in[f].resize(px_count * 2);
+        for (size_t i = 0; i < px_count; ++i) pp_in[f][2 * i] = rgb[3 * i], pp_in[f][2 * i + 1] = rgb[3 * i + 1];
+    }
+    for (auto& v : pp_out) v.resize(px_count * 2);
     if (tiled) {
         const int rc = run_tiled(o, cfg, cam, noisy, normals, positions, albedos, out);
         if (rc != 0) return rc;
@@ -632,6 +660,8 @@ int run(const Options& o) {
         return hipEventRecord(uploaded[f], s);
     };
 
+    float* d_prev_pixel = nullptr;
+    if (!pp_in.empty()) HIP_CHECK(hipMalloc(&d_prev_pixel, px_count * 2 * sizeof(float)));
     BMFR_CHECK(bmfr_set_profiling(ctx, 1, F));
     std::printf("Processing %d frames (%dx%d, B=%d).\n", F, W, H, cfg.features_not_scaled + cfg.features_scaled + 3);
     const auto t0 = std::chrono::steady_clock::now();
@@ -641,10 +671,21 @@ int run(const Options& o) {
         HIP_CHECK(hipStreamWaitEvent(compute, uploaded[f], 0));
         float** d = dev[f % kRing];
         float** pv = dev[(f + kRing - 1) % kRing];
-        bmfr_frame_inputs in = {d[0], d[1], d[2], d[3], f > 0 ? pv[1] : nullptr, f > 0 ? pv[2] : nullptr};
+        bmfr_frame_inputs in = {d[0], d[1], d[2], d[3], f > 0 ? pv[1] : nullptr, f > 0 ? pv[2] : nullptr, nullptr};
+        if (f > 0 && d_prev_pixel) {  // stream order: the previous frame has read the buffer
+            HIP_CHECK(hipMemcpyAsync(d_prev_pixel, pp_in[f].data(), px_count * 2 * sizeof(float), hipMemcpyHostToDevice,
+                                     compute));
+            in.prev_pixel = d_prev_pixel;
+        }
         const int matrix_index = f == 0 ? 0 : f - 1;  // bmfr.cpp:440
         BMFR_CHECK(bmfr_process_frame(ctx, compute, &in, &cam.matrices[16 * matrix_index], &cam.offsets[2 * f], f));
         HIP_CHECK(hipEventRecord(consumed[f], compute));
+        if (!pp_out.empty()) {
+            bmfr_state_view sv;
+            BMFR_CHECK(bmfr_state(ctx, 0, &sv));
+            HIP_CHECK(hipMemcpyAsync(pp_out[f].data(), sv.prev_frame_pixel, px_count * 2 * sizeof(float),
+                                     hipMemcpyDeviceToHost, compute));
+        }
         // Not timed upstream either: the result goes to the frame buffer (bmfr.cpp:478-480).
         HIP_CHECK(hipMemcpyAsync(out[f].data(), bmfr_output(ctx), plane * sizeof(float), hipMemcpyDeviceToHost,
                                  compute));
@@ -696,9 +737,20 @@ int run(const Options& o) {
         if (cnt) std::printf("PSNR vs %s*: mean %.3f dB over %d frames\n", o.psnr.c_str(), sum / cnt, cnt);
     }
 
+    // ---- The previous-frame pixel planes (--dump-prev-pixel): lossless FLOAT EXR ----
+    error = false;
+    for (int f = 0; f < (int)pp_out.size(); ++f) {
+        std::vector<float> rgb(plane, 0.f);
+        for (size_t i = 0; i < px_count; ++i) rgb[3 * i] = pp_out[f][2 * i], rgb[3 * i + 1] = pp_out[f][2 * i + 1];
+        const std::string name = frame_file(o.dump_prev_pixel, f, ".exr");
+        if (bmfr_exr_write_rgb(name.c_str(), W, H, rgb.data(), (size_t)W * 3, BMFR_EXR_ZIP) != 0) {
+            std::printf("Can't create image file on disk to location %s\n", name.c_str());
+            error = true;
+        }
+    }
+
     // ---- Store results (bmfr.cpp:519-553) ----
     if (o.save) {
-        error = false;
 #pragma omp parallel for
         for (int f = 0; f < F; ++f) {
             const std::string name = frame_file(o.output, f, o.exr ? ".exr" : ".png");
@@ -714,6 +766,7 @@ int run(const Options& o) {
     }
 
     for (void* p : registered) (void)hipHostUnregister(p);
+    (void)hipFree(d_prev_pixel);
     for (auto& s : dev)
         for (auto& p : s) (void)hipFree(p);
     for (int f = 0; f < F; ++f) {

@@ -227,7 +227,70 @@ typedef struct bmfr_frame_inputs {  /* float3 planes, or half3 with input_half *
     const void *albedo;
     const void *prev_normals;    /* previous frame's normals (ignored at frame 0) */
     const void *prev_positions;  /* previous frame's positions (ignored at frame 0) */
+    const float *prev_pixel;     /* optional per-pixel previous-frame pixel positions, see below (ignored at frame 0) */
 } bmfr_frame_inputs;
+
+/* prev_pixel: where each pixel was in the previous frame, for content the one
+ * camera matrix cannot describe (moving or skinned objects, camera cuts, a
+ * renderer with its own motion vectors).  NULL (a zero-initialised struct
+ * that fills the first six members): the library projects `positions` through
+ * prev_frame_camera_matrix, as the reference does (bmfr.cl:343-358).
+ *
+ * Layout: a float2 plane, always f32 -- also with input_half (half cannot
+ * hold a 4K pixel coordinate with sub-pixel precision) --, W x H entries, or
+ * the region (bmfr_sizes.region_*) with row stride region_width for a tiled
+ * context.  Entry [y][x] = (pfx, pfy) is the previous-frame position of
+ * pixel (x, y), in the coordinates of the value the library itself stores in
+ * bmfr_state_view.prev_frame_pixel:
+ *     pfx = u * W - jx,      pfy = v * H - (1 - jy),
+ * with (u, v) in [0, 1]^2 the previous frame's screen position of the
+ * pixel's surface point (u to the right, v in the direction of increasing
+ * row index) and (jx, jy) = pixel_offset, the CURRENT frame's jitter.
+ * Integer values are previous-frame pixel indices: (pfx, pfy) = (x, y)
+ * means "was exactly at pixel (x, y)"; the four bilinear taps are
+ * (floor(pfx) + {0,1}, floor(pfy) + {0,1}).
+ *
+ * From a renderer's screen-space motion vector (mx, my), in pixels, pointing
+ * from the previous to the current screen position of a surface point: if
+ * that point is seen at screen position (sx, sy) now (pixels, sx = u * W),
+ * it was at (sx - mx, sy - my), so  pfx = sx - mx - jx,  pfy = sy - my -
+ * (1 - jy).  Where (sx, sy) is depends on where the renderer samples pixel
+ * (x, y):
+ *   - at the jittered position this library assumes, (x + jx, y + 1 - jy)
+ *     (the inverse of bmfr.cl:343-355): the jitter cancels,
+ *         pfx = x - mx,  pfy = y - my;
+ *   - at the pixel centre (x + 0.5, y + 0.5), unjittered vectors:
+ *         pfx = x + 0.5 - mx - jx,  pfy = y + 0.5 - my - (1 - jy)
+ *     (with the offset (0.5, 0.5) the two agree).
+ * A static point under a static camera has (mx, my) = 0 and maps to itself.
+ * Vectors in NDC units scale by W / 2 and H / 2 first; negate my if the
+ * renderer's v grows against the row index.
+ *
+ * When prev_pixel is non-NULL and frame_number > 0 the kernels read neither
+ * prev_frame_camera_matrix (which must still be non-NULL) nor pixel_offset
+ * for reprojection.  Margin work-items (mirrored pixels, bmfr.cl:310-317)
+ * read the plane at the mirrored pixel, as they read normals and positions.
+ * An entry may be any float: taps outside the image are ignored, and an
+ * entry all of whose taps are (far off, +-inf, NaN) restarts the pixel's
+ * history -- spp 1, accumulated colour = current colour -- exactly as an
+ * off-screen projection does.  In a tiled context the reach check applies to
+ * the plane's taps as to projected ones (BMFR_ERROR_HALO_EXCEEDED).
+ *
+ * The plane only says WHERE to look.  Whether a tap is accepted is still the
+ * reference's test of prev_positions / prev_normals at the tap against the
+ * pixel's current position / normal (bmfr.cl:380-404).  For moving content
+ * the caller therefore passes prev_positions and prev_normals moved into the
+ * current frame's world: the previous frame's surface points transformed by
+ * each object's motion since then, so that the tests compare like with like.
+ * (For a static world they are simply the previous frame's planes.)
+ *
+ * Honoured by bmfr_process_frame, _interior / _border and
+ * bmfr_process_sequence (per frame: NULL for some frames, set for others; a
+ * sequence frame that carries a plane runs K1 and the previous frame's TAA as
+ * two launches instead of one, with the same results).  The library keeps
+ * writing bmfr_state_view.prev_frame_pixel: feeding a context the plane
+ * another context computed reproduces that context bit for bit.  The stage
+ * API is unchanged. */
 
 /* prev_frame_camera_matrix: column-major view-projection of frame-1
  * (camera_matrices[max(frame-1,0)], bmfr.cpp:440-442); pixel_offset: the
