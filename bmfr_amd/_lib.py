@@ -78,6 +78,31 @@ class FrameInputs(C.Structure):
                  "prev_pixel")]  # prev_pixel: optional float2 plane (include/bmfr.h), None = project
 
 
+# bmfr_format: element formats of G-buffer planes
+FORMAT_NONE, FORMAT_F32X3, FORMAT_F16X4, FORMAT_UNORM8X4, FORMAT_OCT_SNORM16X2, FORMAT_F32X2, FORMAT_F16X2 = range(7)
+
+
+class GBuffer(C.Structure):
+    """bmfr_gbuffer: what the renderer has (include/bmfr.h)."""
+    _fields_ = [
+        ("radiance", C.c_void_p), ("radiance_format", C.c_int),
+        ("albedo", C.c_void_p), ("albedo_format", C.c_int), ("albedo_floor", C.c_float),
+        ("normals", C.c_void_p), ("normal_format", C.c_int),
+        ("positions", C.c_void_p), ("depth", C.c_void_p), ("inv_view_proj", C.c_float * 16),
+        ("motion", C.c_void_p), ("motion_format", C.c_int), ("motion_scale", C.c_float * 2),
+        ("motion_at_pixel_centre", C.c_int),
+        ("prev_positions", C.c_void_p), ("prev_normals", C.c_void_p), ("prev_object_id", C.c_void_p),
+        ("object_transforms", C.c_void_p), ("n_objects", C.c_int),
+    ]
+
+
+class Prepared(C.Structure):
+    """bmfr_prepared: the outputs of bmfr_prepare_frame (include/bmfr.h)."""
+    _fields_ = [(n, C.c_void_p) for n in
+                ("noisy", "normals", "positions", "albedo", "prev_pixel", "prev_positions_moved",
+                 "prev_normals_moved")]
+
+
 class StateView(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("noisy_accumulated", "spp", "filtered_accumulated", "tone_mapped",
@@ -108,6 +133,8 @@ SIGNATURES = {
     "bmfr_taa": (_I, [_P, _P, _P, _P, _P, _P, _I]),
     "bmfr_process_frame": (_I, [_P, _P, C.POINTER(FrameInputs), _F16, _F2, _I]),
     "bmfr_process_frame_interior": (_I, [_P, _P, C.POINTER(FrameInputs), _F16, _F2, _I]),
+    "bmfr_gbuffer_default": (None, [C.POINTER(GBuffer)]),
+    "bmfr_prepare_frame": (_I, [_P, _P, C.POINTER(GBuffer), C.POINTER(Prepared), _F2]),
     "bmfr_halo_copy": (_I, [_P, _P, C.POINTER(C.c_int), _I, _P, _I, C.POINTER(C.c_size_t)]),
     "bmfr_halo_need": (_I, [C.POINTER(Config), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmfr_process_sequence": (_I, [_P, _P, _I, C.POINTER(FrameInputs), _F16, _F2, _I, C.POINTER(_P)]),

@@ -9,10 +9,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/bmfr.h"
 #include "../../include/bmfr_debug.h"
 #include "bmfr_launch.h"
+#include "bmfr_prepare.h"
 
 using bmfr::Params;
 
@@ -928,6 +930,89 @@ bmfr_status bmfr_process_frame_border(bmfr_ctx* c, void* stream, const bmfr_fram
                                       const float prev_frame_camera_matrix[16], const float pixel_offset[2],
                                       int frame_number) {
     return process_part(c, stream, in, prev_frame_camera_matrix, pixel_offset, frame_number, 1);
+}
+
+// ------------------------------------------------- G-buffer front end ----
+void bmfr_gbuffer_default(bmfr_gbuffer* g) {
+    if (!g) return;
+    std::memset(g, 0, sizeof *g);
+    g->albedo_floor = 1.0f / 255.0f;
+    g->motion_scale[0] = g->motion_scale[1] = 1.0f;
+}
+
+namespace {
+
+// A non-null plane's format must be one of `listed`.
+bool format_listed(const void* plane, int format, std::initializer_list<int> listed) {
+    return !plane || std::find(listed.begin(), listed.end(), format) != listed.end();
+}
+
+// g and out alone (no context, no device): a requested output whose inputs
+// are missing is an invalid argument, an unlisted format unsupported.
+bmfr_status check_prepare_args(const bmfr_gbuffer* g, const bmfr_prepared* out, const float* off) {
+    if (!g || !out || !off) return BMFR_ERROR_INVALID_ARGUMENT;
+    if (g->n_objects < 0 || g->n_objects > 65535 || (g->n_objects > 0 && !g->object_transforms))
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    const bool moved = out->prev_positions_moved || out->prev_normals_moved;
+    if ((out->noisy && (!g->radiance || !g->albedo)) || (out->albedo && !g->albedo) ||
+        (out->normals && !g->normals) || (out->positions && !g->positions && !g->depth) ||
+        (out->prev_pixel && !g->motion) || (out->prev_positions_moved && !g->prev_positions) ||
+        (out->prev_normals_moved && !g->prev_normals) || (moved && g->n_objects > 0 && !g->prev_object_id))
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    if (!format_listed(g->radiance, g->radiance_format, {BMFR_FORMAT_F32X3, BMFR_FORMAT_F16X4}) ||
+        !format_listed(g->albedo, g->albedo_format, {BMFR_FORMAT_F32X3, BMFR_FORMAT_F16X4, BMFR_FORMAT_UNORM8X4}) ||
+        !format_listed(g->normals, g->normal_format,
+                       {BMFR_FORMAT_F32X3, BMFR_FORMAT_F16X4, BMFR_FORMAT_OCT_SNORM16X2}) ||
+        !format_listed(g->motion, g->motion_format, {BMFR_FORMAT_F32X2, BMFR_FORMAT_F16X2}))
+        return BMFR_ERROR_UNSUPPORTED;
+    return BMFR_OK;
+}
+
+}  // namespace
+
+bmfr_status bmfr_prepare_frame(bmfr_ctx* c, void* stream, const bmfr_gbuffer* g, const bmfr_prepared* out,
+                               const float pixel_offset[2]) {
+    const bmfr_status st = check_prepare_args(g, out, pixel_offset);
+    if (st != BMFR_OK) return st;
+    if (!c) return BMFR_ERROR_INVALID_ARGUMENT;
+    bmfr::PrepareArgs a{};
+    a.radiance = g->radiance;
+    a.albedo = g->albedo;
+    a.normals = g->normals;
+    a.positions = g->positions;
+    a.depth = g->depth;
+    a.motion = g->motion;
+    a.prev_positions = g->prev_positions;
+    a.prev_normals = g->prev_normals;
+    a.prev_id = g->prev_object_id;
+    a.transforms = g->object_transforms;
+    a.o_noisy = out->noisy;
+    a.o_normals = out->normals;
+    a.o_positions = out->positions;
+    a.o_albedo = out->albedo;
+    a.o_prev_pixel = out->prev_pixel;
+    a.o_prev_positions = out->prev_positions_moved;
+    a.o_prev_normals = out->prev_normals_moved;
+    std::memcpy(a.m, g->inv_view_proj, sizeof a.m);
+    a.albedo_floor = g->albedo_floor;
+    a.mscale_x = g->motion_scale[0];
+    a.mscale_y = g->motion_scale[1];
+    a.jx = pixel_offset[0];
+    a.jy1 = 1.0f - pixel_offset[1];
+    a.radiance_fmt = g->radiance_format;
+    a.albedo_fmt = g->albedo_format;
+    a.normal_fmt = g->normal_format;
+    a.motion_fmt = g->motion_format;
+    a.motion_centre = g->motion_at_pixel_centre != 0;
+    a.n_objects = g->n_objects;
+    a.rx = c->sizes.region_x;
+    a.ry = c->sizes.region_y;
+    a.rw = c->sizes.region_width;
+    a.W = c->cfg.image_width;
+    a.H = c->cfg.image_height;
+    a.n = (uint32_t)c->sizes.region_width * (uint32_t)c->sizes.region_height;
+    DeviceGuard guard(c->device);
+    return hip_status(bmfr::launch_prepare(a, c->cfg.input_half != 0, static_cast<hipStream_t>(stream)));
 }
 
 bmfr_status bmfr_halo_copy(bmfr_ctx* c, void* stream, const int* rects, int n, void* buffer, int unpack,

@@ -295,6 +295,140 @@ class Denoiser(_Context):
         self._call("bmfr_process_frame_border", noisy, normals, positions, albedo, prev_vp, jitter, frame,
                    prev_normals, prev_positions, stream, True, prev_pixel)
 
+    # ---- G-buffer front end (include/bmfr.h bmfr_prepare_frame) ----
+    # g key -> (bmfr_gbuffer format field, {tensor dtype: (bmfr_format, elements per pixel)})
+    _GBUFFER_PLANES = {
+        "radiance": ("radiance_format", {torch.float32: (_lib.FORMAT_F32X3, 3), torch.float16: (_lib.FORMAT_F16X4, 4)}),
+        "albedo": ("albedo_format", {torch.float32: (_lib.FORMAT_F32X3, 3), torch.float16: (_lib.FORMAT_F16X4, 4),
+                                     torch.uint8: (_lib.FORMAT_UNORM8X4, 4)}),
+        "normals": ("normal_format", {torch.float32: (_lib.FORMAT_F32X3, 3), torch.float16: (_lib.FORMAT_F16X4, 4),
+                                      torch.int16: (_lib.FORMAT_OCT_SNORM16X2, 2)}),
+        "motion": ("motion_format", {torch.float32: (_lib.FORMAT_F32X2, 2), torch.float16: (_lib.FORMAT_F16X2, 2)}),
+        "positions": (None, {torch.float32: (None, 3)}),
+        "depth": (None, {torch.float32: (None, 1)}),
+        "prev_object_id": (None, {torch.int16: (None, 1), getattr(torch, "uint16", torch.int16): (None, 1)}),
+    }
+    _PREPARED = ("noisy", "normals", "positions", "albedo", "prev_pixel", "prev_positions_moved",
+                 "prev_normals_moved")
+
+    def _check_plane(self, name: str, t, dtypes):
+        """A plane handed to the library: a contiguous tensor on this GPU of
+        one of `dtypes` (dtype -> (format, elements per pixel)) covering the
+        region.  Runs before the call, which would read a wrong plane out of
+        bounds.  -> the dtype's format."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor, not {type(t).__name__}")
+        if t.dtype not in dtypes:
+            raise TypeError(f"{name} must be one of {[str(d) for d in dtypes]}, not {t.dtype}")
+        fmt, per = dtypes[t.dtype]
+        n = self.sizes.region_width * self.sizes.region_height * per
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous with {n} elements, not {tuple(t.shape)}")
+        if t.device.type != "cuda" or (t.device.index or 0) != self.device:
+            raise ValueError(f"{name} must live on cuda:{self.device}, not {t.device}")
+        return fmt
+
+    def prepare(self, g: dict, jitter, out: dict | None = None, stream=None) -> dict:
+        """bmfr_prepare_frame: a renderer's G-buffer -> the planes process_frame
+        takes, in one kernel launch (arguments: prepare_args).  -> out."""
+        gb, pr, out = self.prepare_args(g, out)
+        check(self.lib.bmfr_prepare_frame(self.handle, _stream(stream), C.byref(gb), C.byref(pr), floats(jitter, 2)),
+              "bmfr_prepare_frame")
+        return out
+
+    def prepare_args(self, g: dict, out: dict | None = None):
+        """The checked arguments of bmfr_prepare_frame -> (bmfr_gbuffer,
+        bmfr_prepared, out); a caller that repeats a call keeps them.  g: tensors over the region by name --
+        radiance, albedo, normals, positions or depth (with inv_view_proj, 16
+        floats column-major), motion, prev_positions, prev_normals,
+        prev_object_id (int16 / uint16 bits), object_transforms (float32,
+        12 per object) -- and the scalars albedo_floor, motion_scale,
+        motion_at_pixel_centre; a plane's format follows from its dtype
+        (float32 / float16 = RGBA16F or RG16F / uint8 = UNORM8X4 / int16 =
+        octahedral).  out: the outputs to compute by name (noisy, normals,
+        positions, albedo, prev_pixel, prev_positions_moved,
+        prev_normals_moved); None: every output whose inputs are in g,
+        allocated in the context's input format."""
+        gb = _lib.GBuffer()
+        self.lib.bmfr_gbuffer_default(C.byref(gb))
+        for name, (fmt_field, dtypes) in self._GBUFFER_PLANES.items():
+            t = g.get(name)
+            if t is None:
+                continue
+            fmt = self._check_plane(name, t, dtypes)
+            setattr(gb, name, t.data_ptr())
+            if fmt_field:
+                setattr(gb, fmt_field, fmt)
+        plane_dtype = torch.float16 if self.cfg.input_half else torch.float32
+        for name in ("prev_positions", "prev_normals"):
+            if g.get(name) is not None:
+                self._check_plane(name, g[name], {plane_dtype: (None, 3)})
+                setattr(gb, name, g[name].data_ptr())
+        tr = g.get("object_transforms")
+        if tr is not None:
+            if not isinstance(tr, torch.Tensor) or tr.dtype != torch.float32 or tr.numel() % 12 or \
+                    not tr.is_contiguous() or tr.device.type != "cuda" or (tr.device.index or 0) != self.device:
+                raise ValueError("object_transforms must be a contiguous float32 tensor of 12 floats per object "
+                                 f"on cuda:{self.device}")
+            gb.object_transforms, gb.n_objects = tr.data_ptr(), tr.numel() // 12
+        if g.get("inv_view_proj") is not None:
+            gb.inv_view_proj[:] = [float(v) for v in g["inv_view_proj"]]
+        if "albedo_floor" in g:
+            gb.albedo_floor = g["albedo_floor"]
+        if "motion_scale" in g:
+            gb.motion_scale[:] = [float(v) for v in g["motion_scale"]]
+        gb.motion_at_pixel_centre = int(g.get("motion_at_pixel_centre", 0))
+        if out is None:
+            has = lambda *names: all(g.get(n) is not None for n in names)  # noqa: E731
+            want = {"noisy": has("radiance", "albedo"), "albedo": has("albedo"), "normals": has("normals"),
+                    "positions": has("positions") or has("depth"), "prev_pixel": has("motion"),
+                    "prev_positions_moved": has("prev_positions"), "prev_normals_moved": has("prev_normals")}
+            n = self.sizes.region_width * self.sizes.region_height
+            dev = torch.device("cuda", self.device)
+            out = {k: torch.empty(n * 2, dtype=torch.float32, device=dev) if k == "prev_pixel" else
+                   torch.empty(n * 3, dtype=plane_dtype, device=dev) for k, w in want.items() if w}
+        pr = _lib.Prepared()
+        for name, t in out.items():
+            if name not in self._PREPARED:
+                raise KeyError(f"unknown prepared plane {name!r}")
+            self._check_plane(name, t, {torch.float32: (None, 2)} if name == "prev_pixel" else {plane_dtype: (None, 3)})
+            setattr(pr, name, t.data_ptr())
+        return gb, pr, out
+
+    def process_gbuffer(self, g: dict, prev_vp, jitter, frame: int, stream=None) -> None:
+        """prepare(g), then process_frame on the prepared planes.  The
+        denoiser owns two sets of prepared planes and alternates them: K1 of
+        frame f + 1 reads frame f's normals and positions, which must stay
+        unmodified until then.  From frame 1 on: with object_transforms or
+        prev_object_id in g, last frame's planes moved by them are the
+        previous planes, else last frame's planes as they are; with motion in
+        g, the prepared prev_pixel replaces the projection through prev_vp."""
+        n = self.sizes.region_width * self.sizes.region_height
+        if getattr(self, "_prepared_sets", None) is None:
+            dev = torch.device("cuda", self.device)
+            dt = torch.float16 if self.cfg.input_half else torch.float32
+            self._prepared_sets = [{k: torch.empty(n * (2 if k == "prev_pixel" else 3),
+                                                   dtype=torch.float32 if k == "prev_pixel" else dt, device=dev)
+                                    for k in self._PREPARED} for _ in range(2)]
+        cur, last = self._prepared_sets[frame % 2], self._prepared_sets[1 - frame % 2]
+        g = dict(g)
+        want = ["noisy", "normals", "positions", "albedo"]
+        moving = g.get("object_transforms") is not None or g.get("prev_object_id") is not None
+        prev_normals, prev_positions, prev_pixel = last["normals"], last["positions"], None
+        if frame > 0:
+            if moving:
+                g["prev_positions"], g["prev_normals"] = last["positions"], last["normals"]
+                want += ["prev_positions_moved", "prev_normals_moved"]
+                prev_positions, prev_normals = cur["prev_positions_moved"], cur["prev_normals_moved"]
+            if g.get("motion") is not None:
+                want.append("prev_pixel")
+                prev_pixel = cur["prev_pixel"]
+        self.prepare(g, jitter, out={k: cur[k] for k in want}, stream=stream)
+        self.process_frame(cur["noisy"], cur["normals"], cur["positions"], cur["albedo"], prev_vp, jitter, frame,
+                           prev_normals=prev_normals if frame > 0 else None,
+                           prev_positions=prev_positions if frame > 0 else None, stream=stream,
+                           prev_pixel=prev_pixel)
+
     def halo_status(self) -> int:
         """Tiled contexts: waits for the last frame; the largest distance (px)
         by which a frame since frame 0 reprojected past its valid state (0 =

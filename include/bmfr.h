@@ -290,7 +290,11 @@ typedef struct bmfr_frame_inputs {  /* float3 planes, or half3 with input_half *
  * two launches instead of one, with the same results).  The library keeps
  * writing bmfr_state_view.prev_frame_pixel: feeding a context the plane
  * another context computed reproduces that context bit for bit.  The stage
- * API is unchanged. */
+ * API is unchanged.
+ *
+ * bmfr_prepare_frame (below) computes this plane from a renderer's motion
+ * vectors, both cases above, and moves prev_positions / prev_normals by one
+ * rigid transform per object, on the GPU. */
 
 /* prev_frame_camera_matrix: column-major view-projection of frame-1
  * (camera_matrices[max(frame-1,0)], bmfr.cpp:440-442); pixel_offset: the
@@ -332,6 +336,129 @@ bmfr_status bmfr_process_frame_border(bmfr_ctx *ctx, void *stream, const bmfr_fr
 bmfr_status bmfr_process_sequence(bmfr_ctx *ctx, void *stream, int count, const bmfr_frame_inputs *in,
     const float *prev_frame_camera_matrices, const float *pixel_offsets, int first_frame,
     float *const *outputs);
+
+/* ---- G-buffer front end: from a renderer's buffers to bmfr_frame_inputs ----
+ * (no reference counterpart: the reference reads a dataset that already holds
+ * demodulated colour, world positions and float3 normals, bmfr.cpp:137-176).
+ *
+ * bmfr_prepare_frame turns what a renderer has -- radiance and albedo, a
+ * depth buffer and a camera, packed normals, screen-space motion vectors, an
+ * object id per pixel with one rigid transform per object -- into the planes
+ * bmfr_process_frame takes, in one streaming kernel launch on `stream`.
+ *
+ * Planes: every G-buffer plane and every output covers the context's region
+ * (bmfr_sizes.region_*; the whole image when untiled), row stride
+ * region_width, one element per pixel in the plane's bmfr_format.  Pointers
+ * are device memory aligned to the element's natural alignment (planes aligned
+ * to 16 bytes take the kernel's wide accesses).  Outputs must not overlap
+ * inputs.  Output planes are float3, or half3 in an input_half context (the
+ * format bmfr_process_frame of that context reads); prev_pixel is always f32.
+ * The same holds for the inputs prev_positions / prev_normals: they are a
+ * previous call's PREPARED planes.  Below, (x, y) are IMAGE coordinates
+ * (region_x + column, region_y + row), W x H the whole frame, (jx, jy) =
+ * pixel_offset, the frame's jitter.
+ *
+ * Arithmetic: every line is one f32 operation rounded once, associated as
+ * written, never contracted; division and square root correctly rounded;
+ * half / unorm / snorm widen exactly; a half3 output is the f32 result
+ * rounded to nearest even.
+ *
+ *  noisy, albedo <- radiance, albedo.  Per channel, a = the albedo as f32,
+ *      d = (a > albedo_floor) ? a : albedo_floor   (a NaN albedo takes the floor)
+ *      noisy = radiance / d;   albedo = a          (not floored: K2 remodulates
+ *                                                    with the true albedo)
+ *  positions <- positions (copied, narrowed for half3), or, when that is
+ *      NULL, depth: the clip-space z / w inv_view_proj expects, with the
+ *      pixel's sample at screen position (x + jx, y + 1 - jy), the inverse
+ *      of the reprojection's convention (bmfr.cl:343-355):
+ *      sx = float(x) + jx;              sy = float(y) + (1.0f - jy)
+ *      nx = (sx / float(W)) * 2.0f - 1.0f;   ny likewise with H
+ *      h_i = ((m[i]*nx + m[4+i]*ny) + m[8+i]*depth) + m[12+i],  i = 0..3
+ *      position_i = h_i / h_3           (m = inv_view_proj, column-major)
+ *  normals <- normals.  F32X3 / F16X4 pass through (not renormalised).
+ *      OCT_SNORM16X2, per component e = float(s16) / 32767.0f, below -1: -1,
+ *      z = (1.0f - |ex|) - |ey|
+ *      z < 0:  ox = (1.0f - |ey|) * (ex >= 0 ? 1 : -1),
+ *              oy = (1.0f - |ex|) * (ey >= 0 ? 1 : -1);   else (ox, oy) = (ex, ey)
+ *      len = sqrt((ox*ox + oy*oy) + z*z);   n = (ox / len, oy / len, z / len)
+ *  prev_pixel <- motion, the screen-space vector from the previous to the
+ *      current position of the pixel's surface point:
+ *      mx = mvx * motion_scale[0];   my = mvy * motion_scale[1]
+ *      motion_at_pixel_centre = 0 (vector taken at the jittered sample):
+ *          pfx = float(x) - mx;   pfy = float(y) - my
+ *      motion_at_pixel_centre = 1 (at (x + 0.5, y + 0.5)):
+ *          pfx = ((float(x) + 0.5f) - mx) - jx
+ *          pfy = ((float(y) + 0.5f) - my) - (1.0f - jy)
+ *      -- the two cases of the prev_pixel comment above.  Any motion value
+ *      is legal (K1 makes any plane entry safe).
+ *  prev_positions_moved, prev_normals_moved <- prev_positions, prev_normals,
+ *      prev_object_id, object_transforms: the previous frame's planes moved
+ *      into the current frame's world.  id = prev_object_id[pixel]; if id <
+ *      n_objects, with M = object_transforms + 12 * id (row-major 3x4,
+ *      previous world -> current world, a rigid motion: no renormalisation,
+ *      no inverse transpose):
+ *          p'_i = ((M[4i]*p.x + M[4i+1]*p.y) + M[4i+2]*p.z) + M[4i+3]
+ *          n'_i =  (M[4i]*n.x + M[4i+1]*n.y) + M[4i+2]*n.z
+ *      otherwise (ids at or past the table -- 0xFFFF is never in it --, or
+ *      n_objects = 0, for which prev_object_id may be NULL) the pixel is
+ *      copied unchanged, byte for byte.
+ *
+ * Each non-NULL member of bmfr_prepared is computed.  Returns
+ * BMFR_ERROR_INVALID_ARGUMENT for a NULL g / out / pixel_offset, a requested
+ * output one of whose inputs is NULL, n_objects outside 0..65535 or n_objects
+ * > 0 with NULL object_transforms, and for a NULL ctx;
+ * BMFR_ERROR_UNSUPPORTED for a non-NULL plane whose format is not listed for
+ * it below.  g and out are checked first, in that order, so they can be
+ * validated without a context.  A call that requests nothing launches nothing
+ * and returns BMFR_OK.  Costs about one device copy of the same bytes
+ * (DESIGN.md "G-buffer front end"). */
+typedef enum bmfr_format {       /* element formats of G-buffer planes */
+    BMFR_FORMAT_NONE = 0,
+    BMFR_FORMAT_F32X3,           /* interleaved, 12 B/px (the library's own float3 planes) */
+    BMFR_FORMAT_F16X4,           /* 8 B/px, 4th component ignored (RGBA16F) */
+    BMFR_FORMAT_UNORM8X4,        /* 4 B/px, v / 255, 4th ignored; albedo only */
+    BMFR_FORMAT_OCT_SNORM16X2,   /* 4 B/px octahedral unit vector; normals only */
+    BMFR_FORMAT_F32X2,           /* 8 B/px; motion only */
+    BMFR_FORMAT_F16X2            /* 4 B/px; motion only */
+} bmfr_format;
+
+typedef struct bmfr_gbuffer {    /* what the renderer has; every pointer nullable */
+    const void *radiance;        /* F32X3 | F16X4 */
+    int radiance_format;
+    const void *albedo;          /* F32X3 | F16X4 | UNORM8X4 */
+    int albedo_format;
+    float albedo_floor;          /* demodulation guard */
+    const void *normals;         /* F32X3 | F16X4 | OCT_SNORM16X2 */
+    int normal_format;
+    const float *positions;      /* F32X3 world positions, or NULL and: */
+    const float *depth;          /* f32, the clip-space z / w inv_view_proj expects */
+    float inv_view_proj[16];     /* column-major inverse of THIS frame's view-projection */
+    const void *motion;          /* F32X2 | F16X2, previous -> current screen position */
+    int motion_format;
+    float motion_scale[2];       /* to pixels: (1, 1); NDC units: (W / 2, H / 2); negate [1] if v runs against rows */
+    int motion_at_pixel_centre;  /* 0: taken at the jittered sample; 1: at (x + .5, y + .5) */
+    const void *prev_positions;  /* last frame's PREPARED planes (float3, or half3 with input_half) */
+    const void *prev_normals;
+    const uint16_t *prev_object_id;   /* per pixel of the previous frame */
+    const float *object_transforms;   /* n_objects x 12 floats, row-major 3x4, previous world -> current world */
+    int n_objects;
+} bmfr_gbuffer;
+
+typedef struct bmfr_prepared {   /* outputs, nullable; float3 planes, or half3 with input_half */
+    void *noisy;
+    void *normals;
+    void *positions;
+    void *albedo;
+    float *prev_pixel;           /* float2, always f32 */
+    void *prev_positions_moved;
+    void *prev_normals_moved;
+} bmfr_prepared;
+
+/* Zeroes *g; albedo_floor = 1 / 255 (the smallest non-zero 8-bit albedo),
+ * motion_scale = (1, 1). */
+void bmfr_gbuffer_default(bmfr_gbuffer *g);
+bmfr_status bmfr_prepare_frame(bmfr_ctx *ctx, void *stream, const bmfr_gbuffer *g,
+    const bmfr_prepared *out, const float pixel_offset[2]);
 
 /* Halo exchange support for tiled contexts: copy the rectangles rects[n][5]
  * = {x, y, width, height, planes} (image coordinates inside the context's
