@@ -68,6 +68,19 @@ class RefConfig:
         mw, mh = self.margins
         return (mw // 32) * (mh // 32)
 
+    def knobs(self) -> dict:
+        """The six run-time parameters as the values the reference kernel sees
+        in its literals, under the keyword names of BmfrConfig and
+        pyoracle.make_cfg: the alphas are float literals ("0.05f" ->
+        float32(0.05)), NOISE_AMOUNT a double literal; the two limits stay
+        doubles, both sides apply the %g rule themselves."""
+        import numpy as np
+        f32 = lambda t: float(np.float32(float(t.rstrip("fF"))))  # noqa: E731
+        return dict(noise_amount=float(self.noise_amount), blend_alpha=f32(self.blend_alpha),
+                    second_blend_alpha=f32(self.second_blend_alpha), taa_blend_alpha=f32(self.taa_blend_alpha),
+                    position_limit_squared=self.position_limit_squared,
+                    normal_limit_squared=self.normal_limit_squared)
+
     def feature_text(self) -> str:
         return ",".join(FEATURE_TEXT[c] for c in self.not_scaled + self.scaled)
 
@@ -146,6 +159,50 @@ FULL_REF_CONFIGS = {
         RefConfig("f1280x720_h13", 1280, 720, frames=60),                # a whole 60-frame sequence
     )
 }
+
+# The run-time parameter surface away from the reference's defaults
+# (tests/test_knobs_cpu.py, tests/test_gpu_knobs.py).  A set names only what it
+# changes.  tight / loose / ends move all six; the limits of loose and ends are
+# not their own %g text (0.123456789 -> "0.123457", 1.0000049 -> "1").  cut:
+# BLEND_ALPHA 1 keeps spp at 1.  lit: a normal limit whose %g text is "1", on
+# content whose squared normal distance is 1.0000019 (tests/knob_util.py).
+KNOB_SETS = {
+    "tight": dict(noise_amount="1e-3", blend_alpha="0.5f", second_blend_alpha="0.25f", taa_blend_alpha="0.05f",
+                  position_limit_squared=0.0025, normal_limit_squared=3.0),
+    "loose": dict(noise_amount="1e-1", blend_alpha="0.05f", second_blend_alpha="0.02f", taa_blend_alpha="0.5f",
+                  position_limit_squared=0.123456789, normal_limit_squared=1.5),
+    "ends": dict(noise_amount="0.5", blend_alpha="0.0f", second_blend_alpha="0.0f", taa_blend_alpha="1.0f",
+                 position_limit_squared=1.0000049, normal_limit_squared=0.5),
+    "cut": dict(blend_alpha="1.0f"),
+    "lit": dict(normal_limit_squared=1.0000049),
+}
+KNOB_FRAMES = 14  # SECOND_BLEND_ALPHA 0.1 caps 1 / spp from spp 11 on
+
+
+def _knob_config(knob_set: str, base: str, frames: int = KNOB_FRAMES) -> RefConfig:
+    """Size, feature list and tmp precision of REF_CONFIGS["s" + base]."""
+    return dataclasses.replace(REF_CONFIGS["s" + base], name=f"k_{knob_set}_{base}", frames=frames,
+                               **KNOB_SETS[knob_set])
+
+
+KNOB_REF_CONFIGS = {
+    c.name: c
+    for c in (
+        _knob_config("tight", "128x80_h13"),
+        _knob_config("tight", "128x80_f13"),
+        _knob_config("loose", "100x72_h16"),
+        _knob_config("loose", "96x64_h7"),   # generic-count K1
+        _knob_config("ends", "128x80_h13"),
+        _knob_config("ends", "100x72_h16"),
+        _knob_config("cut", "128x80_h13"),
+        _knob_config("lit", "128x80_h13", frames=8),
+    )
+}
+
+
+def knob_set_of(name: str) -> str:
+    return name.split("_")[1]
+
 
 # Build modes of the reference: "strict" fixes the arithmetic OpenCL leaves to
 # the implementation (no contraction, correctly rounded / and sqrt) and is the

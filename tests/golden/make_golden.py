@@ -11,7 +11,14 @@ silently compared.  Per frame the fixture keeps
   * tone / result (powr-dependent) as float64 sums and an 8192-element
     strided sample (compared with a tolerance on the CPU side).
 
+Other content and other configurations: make(name, out_dir, configs, scene,
+seed) takes the configuration dictionary and a scene of tests/scenes_np.py; the
+fixture then records the scene, the seed and the six knob texts of the
+configuration.  --knobs makes the fixtures of tests/test_knobs_cpu.py
+(ref_configs.KNOB_REF_CONFIGS on scene rand) under tests/golden/knobs/.
+
 Usage (GPU box): python tests/golden/make_golden.py [--out DIR] [config ...]
+                 python tests/golden/make_golden.py --knobs [--out DIR] [config ...]
 """
 from __future__ import annotations
 
@@ -28,19 +35,40 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import ref_run  # noqa: E402
-from ref_configs import REF_CONFIGS  # noqa: E402
+import knob_util  # noqa: E402
+import scenes_np  # noqa: E402
+from ref_configs import KNOB_REF_CONFIGS, REF_CONFIGS, fmt_g  # noqa: E402
 from seq_util import EXACT_KEYS, POWR_KEYS, digest, frame_inputs, input_digest, run_loop, sample_idx  # noqa: E402
 
 
-def make(name: str, out_dir: str = HERE) -> str:
-    rc = REF_CONFIGS[name]
-    frames = run_loop(ref_run.RefLoop(rc, "strict"), rc, rc.frames,
-                      to_device=lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda(),
-                      sync=torch.cuda.synchronize)
-    meta = {"config": name, "frames": rc.frames, "mode": "strict", "seed": rc.seed,
-            "inputs": [input_digest(frame_inputs(rc, f)) for f in range(rc.frames)],
-            "digests": [{k: digest(fr[k]) for k in EXACT_KEYS} for fr in frames],
-            "stats": []}
+KNOB_GOLDEN = ("k_tight_128x80_h13", "k_loose_100x72_h16")  # tests/test_knobs_cpu.py GOLDEN_NAMES
+
+
+def knob_texts(rc) -> dict:
+    """The six run-time parameters as the reference's -D string carries them."""
+    return {"noise_amount": rc.noise_amount, "blend_alpha": rc.blend_alpha,
+            "second_blend_alpha": rc.second_blend_alpha, "taa_blend_alpha": rc.taa_blend_alpha,
+            "position_limit_squared": fmt_g(rc.position_limit_squared),
+            "normal_limit_squared": fmt_g(rc.normal_limit_squared)}
+
+
+def make(name: str, out_dir: str = HERE, configs=REF_CONFIGS, scene: str | None = None,
+         seed: int | None = None) -> str:
+    """scene None: the synthetic sequence (seed: the configuration's)."""
+    rc = configs[name]
+    dev = lambda a: torch.from_numpy(np.array(a, order="C")).cuda()  # noqa: E731  (a copy: scenes' planes are read-only)
+    if scene is None:
+        frames = run_loop(ref_run.RefLoop(rc, "strict"), rc, rc.frames, to_device=dev, sync=torch.cuda.synchronize)
+        meta = {"seed": rc.seed, "inputs": [input_digest(frame_inputs(rc, f)) for f in range(rc.frames)]}
+    else:
+        frames = scenes_np.run_loop(ref_run.RefLoop(rc, "strict"), scene, rc.width, rc.height, rc.frames, seed,
+                                    to_device=dev, sync=torch.cuda.synchronize)
+        meta = {"scene": scene, "seed": seed, "knobs": knob_texts(rc),
+                "inputs": [knob_util.frame_digest(scenes_np.frame(scene, rc.width, rc.height, f, seed))
+                           for f in range(rc.frames)]}
+    meta.update({"config": name, "frames": rc.frames, "mode": "strict",
+                 "digests": [{k: digest(fr[k]) for k in EXACT_KEYS} for fr in frames],
+                 "stats": []})
     arrays = {}
     for f, fr in enumerate(frames):
         arrays[f"weights_{f}"] = fr["weights"]
@@ -61,7 +89,13 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="*")
-    ap.add_argument("--out", default=HERE, help="output directory (default: tests/golden)")
+    ap.add_argument("--out", help="output directory (default: tests/golden, with --knobs tests/golden/knobs)")
+    ap.add_argument("--knobs", action="store_true", help="the knob fixtures: KNOB_REF_CONFIGS on scene rand")
     a = ap.parse_args()
-    for n in a.configs or list(REF_CONFIGS):
-        print(make(n, a.out), flush=True)
+    if a.knobs:
+        for n in a.configs or KNOB_GOLDEN:
+            assert knob_util.scene_of(n) == ("rand", False), n
+            print(make(n, a.out or os.path.join(HERE, "knobs"), KNOB_REF_CONFIGS, "rand", knob_util.SEED), flush=True)
+    else:
+        for n in a.configs or list(REF_CONFIGS):
+            print(make(n, a.out or HERE), flush=True)

@@ -305,14 +305,16 @@ def frame(scene: str, W: int, H: int, f: int, seed: int = 1, region=None, still:
 
 
 def run_loop(loop, scene: str, W: int, H: int, frames: int, seed: int = 1, to_device=None, sync=None,
-             still: bool = False, prepare=None):
+             still: bool = False, prepare=None, source=None):
     """Drive a frame loop (upload / run_stages / swap) over a scene; returns
     the per-frame records as numpy arrays.  prepare: maps the four planes
-    (numpy, f32) before upload, e.g. a round trip through half."""
+    (numpy, f32) before upload, e.g. a round trip through half.  source: f ->
+    a frame() dict, for content derived from a scene (then scene, seed and
+    still are not used)."""
     from seq_util import to_np
     out = []
     for f in range(frames):
-        fr = frame(scene, W, H, f, seed, still=still)
+        fr = source(f) if source is not None else frame(scene, W, H, f, seed, still=still)
         planes = [fr[k] for k in ("noisy", "normals", "positions", "albedo")]
         if prepare is not None:
             planes = [prepare(p) for p in planes]

@@ -1,5 +1,7 @@
 """C-ABI checks that need no GPU: every symbol include/bmfr.h declares is
-exported, host-side functions behave, device entry points fail cleanly."""
+exported, host-side functions behave, device entry points fail cleanly.  (One
+test, marked gpu, creates a context: bmfr_create at the far ends of the
+run-time parameters.)"""
 from __future__ import annotations
 
 import ctypes as C
@@ -93,6 +95,49 @@ def test_default_config_is_reference_defines():
     # the options beyond the reference's defines default to its behaviour:
     # untiled, f32 inputs, exact fit (library_powr 0 = the correctly rounded powr)
     assert (c.tile_width, c.tile_height, c.input_half, c.library_powr, c.fast_fit) == (0, 0, 0, 0, 0)
+
+
+def _knob_sets():
+    from ref_configs import KNOB_REF_CONFIGS
+    return {n.split("_")[1]: rc.knobs() for n, rc in KNOB_REF_CONFIGS.items()}
+
+
+@pytest.mark.parametrize("knob_set", ["tight", "loose", "ends"])
+def test_non_default_knobs_survive_the_trip_to_bmfr_config(knob_set):
+    """All six run-time parameters away from the defaults, BmfrConfig ->
+    bmfr_config, value for value: the alphas as the float of their literal,
+    noise_amount and the limits as the doubles given (the %g rule of the
+    limits is the library's, applied when it builds its kernel parameters)."""
+    k = _knob_sets()[knob_set]
+    d = bmfr_amd.BmfrConfig()
+    assert all(k[key] != getattr(d, key) for key in k), k
+    c = bmfr_amd.BmfrConfig(image_width=128, image_height=80, **k).to_c()
+    assert c.noise_amount == k["noise_amount"]
+    for key in ("blend_alpha", "second_blend_alpha", "taa_blend_alpha"):
+        assert getattr(c, key) == float(np.float32(k[key])), key
+    assert c.position_limit_squared == k["position_limit_squared"]
+    assert c.normal_limit_squared == k["normal_limit_squared"]
+    # nothing else moved
+    ref = bmfr_amd.BmfrConfig(image_width=128, image_height=80).to_c()
+    for name, _ in _lib.Config._fields_:
+        if name not in k:
+            a, b = getattr(c, name), getattr(ref, name)
+            assert (list(a) == list(b)) if hasattr(a, "__len__") else (a == b), name
+    # alphas of 0 and 1 and a limit beyond 1 are a valid configuration
+    s = _lib.Sizes()
+    assert _lib.load().bmfr_config_sizes(C.byref(c), C.byref(s)) == 0
+
+
+@pytest.mark.gpu
+def test_create_accepts_the_ends_set(gpu):
+    """blend alphas 0 / 0 / 1, noise_amount 0.5, a position limit whose %g text is "1"."""
+    lib = _lib.load()
+    c = bmfr_amd.BmfrConfig(image_width=128, image_height=80, **_knob_sets()["ends"]).to_c()
+    assert (c.blend_alpha, c.second_blend_alpha, c.taa_blend_alpha) == (0.0, 0.0, 1.0)
+    h = C.c_void_p()
+    assert lib.bmfr_create(C.byref(c), 0, C.byref(h)) == 0
+    assert h.value
+    assert lib.bmfr_destroy(h) == 0
 
 
 def test_status_strings():

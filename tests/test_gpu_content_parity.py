@@ -372,6 +372,14 @@ def test_fast_fit_within_tolerance(scene, case, gpu, parity_log):
 def test_tiled_half_inputs_match_untiled(gx, gy, scene, fast_fit, gpu):
     """Tiled contexts have non-zero plane origins and region-sized planes:
     the paired half tap loads there, against the untiled half-input frame."""
+    check_tiled_half_inputs(gx, gy, scene, fast_fit=fast_fit)
+
+
+def check_tiled_half_inputs(gx, gy, scene, split=False, **cfg_kw):
+    """The tiled case: every frame of every tile == the untiled frame bit for
+    bit, the halo report clean.  split: each frame as process_frame_interior,
+    halo exchange, process_frame_border instead of exchange, process_frame.
+    cfg_kw: BmfrConfig keywords of every context, the untiled one included."""
     from bmfr_amd.tiling import HipCopier, LoopbackTransport, TileGrid, state_planes
     W, H, halo = 320, 256, 40
     n = W * H
@@ -380,7 +388,7 @@ def test_tiled_half_inputs_match_untiled(gx, gy, scene, fast_fit, gpu):
     # moves up to 5.9 px at this size
     speed = 0.2 if scene == "pan" else 1.0
     grid = TileGrid(W, H, gx, gy, halo=halo)
-    kw = dict(image_width=W, image_height=H, input_half=1, fast_fit=fast_fit)
+    kw = dict(image_width=W, image_height=H, input_half=1, **cfg_kw)
     full = bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(**kw))
     tiles = [bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(tile=grid.tile(r), tile_halo=halo, **kw))
              for r in range(grid.ranks)]
@@ -396,13 +404,14 @@ def test_tiled_half_inputs_match_untiled(gx, gy, scene, fast_fit, gpu):
         for d in tiles:
             cut = scenes_np.frame(scene, W, H, f, SEED, region=d.region, speed=speed)
             inps.append({k: _dev(cut[k].astype(np.float16)) for k in PLANES})
-        if f > 0:
-            loop.exchange_all([state_planes(d) for d in tiles], copier)
-        for r, d in enumerate(tiles):
-            i = inps[r]
-            d.process_frame(i["noisy"], i["normals"], i["positions"], i["albedo"], vp, jit, f,
-                            prev_normals=prev[r]["normals"] if prev[r] else None,
-                            prev_positions=prev[r]["positions"] if prev[r] else None)
+        for call in ("process_frame_interior", "process_frame_border") if split else ("process_frame",):
+            if f > 0 and call != "process_frame_interior":
+                loop.exchange_all([state_planes(d) for d in tiles], copier)
+            for r, d in enumerate(tiles):
+                i = inps[r]
+                getattr(d, call)(i["noisy"], i["normals"], i["positions"], i["albedo"], vp, jit, f,
+                                 prev_normals=prev[r]["normals"] if prev[r] else None,
+                                 prev_positions=prev[r]["positions"] if prev[r] else None)
         prev = inps
         torch.cuda.synchronize()
         want = {"result": full.copy_output(torch.empty(3 * n, device="cuda")).view(H, W, 3),
