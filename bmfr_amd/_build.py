@@ -20,7 +20,9 @@ SOURCES = ["bmfr_kernels.hip", "bmfr_fused.hip", "bmfr_fused_cols.hip", "bmfr_fu
            "bmfr_fused_plane.hip", "bmfr_fused_cols_plane.hip", "bmfr_fused_cols_f32_plane.hip",
            "bmfr_exchange.hip", "bmfr_prepare.hip",
            "bmfr_synth.hip",
-           "bmfr_generic_ns1.hip", "bmfr_generic_ns2.hip", "bmfr_generic_ns3.hip", "bmfr_generic_ns4.hip"]
+           "bmfr_generic_ns1.hip", "bmfr_generic_ns2.hip", "bmfr_generic_ns3.hip", "bmfr_generic_ns4.hip",
+           "bmfr_generic_aux_ns1.hip", "bmfr_generic_aux_ns2.hip", "bmfr_generic_aux_ns3.hip",
+           "bmfr_generic_aux_ns4.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize",
          "-Wall", "-Wno-unused-function"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC"]

@@ -19,12 +19,15 @@ _variant = os.environ.get("BMFR_LIB", "")
 LIB_PATH = os.path.join(HERE, f"libbmfr_{_variant}.so" if _variant else "libbmfr.so")
 
 MAX_FEATURES = 16
+MAX_AUX_FEATURES = 4
 
 # bmfr_feature
 FEATURE_ONE, NORMAL_X, NORMAL_Y, NORMAL_Z = 0, 1, 2, 3
 POSITION_X, POSITION_Y, POSITION_Z = 4, 5, 6
 POSITION_X2, POSITION_Y2, POSITION_Z2 = 7, 8, 9
 POSITION_X3, POSITION_Y3, POSITION_Z3 = 10, 11, 12
+# caller-supplied feature planes (bmfr_aux_inputs.aux[0..3])
+FEATURE_AUX0, FEATURE_AUX1, FEATURE_AUX2, FEATURE_AUX3 = 13, 14, 15, 16
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "unsupported configuration",
           3: "out of device memory", 4: "HIP runtime error", 5: "no HIP device",
@@ -76,6 +79,11 @@ class FrameInputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("noisy", "normals", "positions", "albedo", "prev_normals", "prev_positions",
                  "prev_pixel")]  # prev_pixel: optional float2 plane (include/bmfr.h), None = project
+
+
+class AuxInputs(C.Structure):
+    """bmfr_aux_inputs: one frame's feature planes FEATURE_AUX0..3 (None = not supplied)."""
+    _fields_ = [("aux", C.c_void_p * MAX_AUX_FEATURES)]
 
 
 # bmfr_format: element formats of G-buffer planes
@@ -139,6 +147,11 @@ SIGNATURES = {
     "bmfr_halo_need": (_I, [C.POINTER(Config), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmfr_process_sequence": (_I, [_P, _P, _I, C.POINTER(FrameInputs), _F16, _F2, _I, C.POINTER(_P)]),
     "bmfr_process_frame_border": (_I, [_P, _P, C.POINTER(FrameInputs), _F16, _F2, _I]),
+    "bmfr_process_frame_aux": (_I, [_P, _P, C.POINTER(FrameInputs), C.POINTER(AuxInputs), _F16, _F2, _I]),
+    "bmfr_process_frame_interior_aux": (_I, [_P, _P, C.POINTER(FrameInputs), C.POINTER(AuxInputs), _F16, _F2, _I]),
+    "bmfr_process_frame_border_aux": (_I, [_P, _P, C.POINTER(FrameInputs), C.POINTER(AuxInputs), _F16, _F2, _I]),
+    "bmfr_process_sequence_aux": (_I, [_P, _P, _I, C.POINTER(FrameInputs), C.POINTER(AuxInputs), _F16, _F2, _I,
+                                       C.POINTER(_P)]),
     "bmfr_output": (_P, [_P]),
     "bmfr_halo_status": (_I, [_P, C.POINTER(C.c_uint)]),
     "bmfr_frame_status": (_I, [_P]),

@@ -143,6 +143,16 @@ bool is_tiled(const bmfr_config* c) { return c->tile_width > 0; }
 size_t done_bytes(const bmfr_ctx* c) { return (size_t)c->P.blocks_x * c->P.blocks_y * sizeof(unsigned); }
 // The stage kernels take the reference's whole-frame f32 layouts only.
 bool stage_api_ok(const bmfr_config* c) { return !is_tiled(c) && !c->input_half; }
+// The stages that evaluate features keep the reference's signatures, which
+// have no place for a caller-supplied plane.
+bool names_aux(const bmfr_ctx* c) { return bmfr::aux_mask(c->P) != 0; }
+// A plane the context's list names must be there (bmfr_aux_inputs, nullable).
+bool aux_planes_ok(const bmfr_ctx* c, const bmfr_aux_inputs* aux) {
+    const int mask = bmfr::aux_mask(c->P);
+    for (int k = 0; k < BMFR_MAX_AUX_FEATURES; ++k)
+        if ((mask & (1 << k)) && (!aux || !aux->aux[k])) return false;
+    return true;
+}
 
 Params make_params(const bmfr_config* c, const bmfr_sizes* s) {
     Params P{};
@@ -460,7 +470,7 @@ bmfr_status bmfr_accumulate_noisy_data(bmfr_ctx* c, void* stream, float* out_pre
         !current_noisy || !current_spp || !tmp_data || !prev_frame_camera_matrix || !pixel_offset ||
         frame_number < 0)
         return BMFR_ERROR_INVALID_ARGUMENT;
-    if (!stage_api_ok(&c->cfg)) return BMFR_ERROR_UNSUPPORTED;
+    if (!stage_api_ok(&c->cfg) || names_aux(c)) return BMFR_ERROR_UNSUPPORTED;
     if (frame_number > 0 && (!previous_normals || !previous_positions || !previous_noisy || !previous_spp))
         return BMFR_ERROR_INVALID_ARGUMENT;
     bmfr::NoisyInputs in{current_normals, previous_normals, current_positions, previous_positions,
@@ -490,7 +500,7 @@ bmfr_status bmfr_weighted_sum(bmfr_ctx* c, void* stream, const float* weights, c
     if (!c || !weights || (!mins_maxs && c->P.scaled > 0) || !output || !current_normals || !current_positions ||
         frame_number < 0)
         return BMFR_ERROR_INVALID_ARGUMENT;
-    if (!stage_api_ok(&c->cfg)) return BMFR_ERROR_UNSUPPORTED;
+    if (!stage_api_ok(&c->cfg) || names_aux(c)) return BMFR_ERROR_UNSUPPORTED;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_weighted_sum(c->P, as_stream(stream), weights, mins_maxs, output,
                                                 current_normals, current_positions, frame_number));
@@ -528,12 +538,13 @@ bmfr_status bmfr_taa(bmfr_ctx* c, void* stream, const float* in_prev_frame_pixel
 // ----------------------------------------------------------- frame API ----
 namespace {
 
-bmfr_status check_frame_args(const bmfr_ctx* c, const bmfr_frame_inputs* in, const float* m, const float* off,
-                             int frame_number) {
+bmfr_status check_frame_args(const bmfr_ctx* c, const bmfr_frame_inputs* in, const bmfr_aux_inputs* aux,
+                             const float* m, const float* off, int frame_number) {
     if (!c || !in || !in->noisy || !in->normals || !in->positions || !in->albedo || !m || !off || frame_number < 0)
         return BMFR_ERROR_INVALID_ARGUMENT;
     if (frame_number > 0 && (!in->prev_normals || !in->prev_positions || !c->has_frame))
         return BMFR_ERROR_INVALID_ARGUMENT;
+    if (!aux_planes_ok(c, aux)) return BMFR_ERROR_INVALID_ARGUMENT;
     if (!bmfr::fitter_supported(c->P.not_scaled, c->P.scaled)) return BMFR_ERROR_UNSUPPORTED;
     if ((is_tiled(&c->cfg) || c->cfg.input_half) && !bmfr::fused_supported(c->P)) return BMFR_ERROR_UNSUPPORTED;
     return BMFR_OK;
@@ -541,7 +552,7 @@ bmfr_status check_frame_args(const bmfr_ctx* c, const bmfr_frame_inputs* in, con
 
 // The kernels' arguments for frame `frame_number`, writing state slot `cur`.
 bmfr::FusedArgs frame_args(const bmfr_ctx* c, const bmfr_frame_inputs* in, const float* m, const float* off,
-                           int frame_number, int cur) {
+                           int frame_number, int cur, const bmfr_aux_inputs* aux = nullptr) {
     const int prv = 1 - cur;
     bmfr::FusedArgs A;
     // Input planes are float3 or (input_half) half3; the kernels read them
@@ -570,6 +581,9 @@ bmfr::FusedArgs frame_args(const bmfr_ctx* c, const bmfr_frame_inputs* in, const
     // The caller's previous-frame pixel plane replaces the projection from
     // frame 1 on (frame 0 has no previous frame: ignored, like prev_normals).
     A.prev_pixel_in = frame_number > 0 ? reinterpret_cast<const float2*>(in->prev_pixel) : nullptr;
+    // The planes the list names; the others are ignored.
+    const int mask = bmfr::aux_mask(c->P);
+    for (int k = 0; k < BMFR_MAX_AUX_FEATURES; ++k) A.aux.p[k] = (aux && (mask & (1 << k))) ? aux->aux[k] : nullptr;
     return A;
 }
 
@@ -699,9 +713,9 @@ bmfr_status next_epoch(bmfr_ctx* c, hipStream_t s, bmfr::FusedArgs* A) {
 
 // PART 0: noise table + interior blocks.  PART 1: border blocks + K2 (+ swap).
 // PART 2: everything (bmfr_process_frame).
-bmfr_status process_part(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in, const float* m,
-                         const float* off, int frame_number, int part) {
-    bmfr_status st = check_frame_args(c, in, m, off, frame_number);
+bmfr_status process_part(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in, const bmfr_aux_inputs* aux,
+                         const float* m, const float* off, int frame_number, int part) {
+    bmfr_status st = check_frame_args(c, in, aux, m, off, frame_number);
     if (st != BMFR_OK) return st;
     if (part == 1 && c->pending_frame != frame_number) return BMFR_ERROR_INVALID_ARGUMENT;
     if (part != 1 && c->pending_frame >= 0) return BMFR_ERROR_INVALID_ARGUMENT;
@@ -709,9 +723,9 @@ bmfr_status process_part(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in,
     if (part != 1 && (st = status_check(c, frame_number)) != BMFR_OK) return st;
     const hipStream_t s = as_stream(stream);
     const int cur = c->has_frame ? 1 - c->cur : 0;  // swap, bmfr.cpp:482-484
-    bmfr::FusedArgs A = frame_args(c, in, m, off, frame_number, cur);
+    bmfr::FusedArgs A = frame_args(c, in, m, off, frame_number, cur, aux);
     const Params P = frame_params(c, frame_number);
-    if (part != 2 && !bmfr::fused_supported(P)) return BMFR_ERROR_UNSUPPORTED;
+    const bool generic = !bmfr::fused_supported(P);  // untiled (check_frame_args): every block is interior
     // Profiling: 3 events of one slot per recorded frame; part 0 takes the
     // slot, part 1 finishes it.
     hipEvent_t* ev = nullptr;
@@ -731,6 +745,19 @@ bmfr_status process_part(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in,
         if (c->done && !ev && (st = next_epoch(c, s, &A)) != BMFR_OK) return st;  // one launch
         st = hip_status(bmfr::launch_fused_frame(P, s, A, ev ? ev[1] : nullptr));
         if (st != BMFR_OK) return st;
+    } else if (generic) {
+        // The generic-feature path's two launches: K1 is the interior part, its TAA the border part.
+        if (part == 0) {
+            if ((st = hip_status(bmfr::launch_fused_generic(P, s, A))) != BMFR_OK) return st;
+            c->pending_frame = frame_number;
+            c->pending_prof_slot = ev ? (int)((c->prof_count - 1) % c->prof_capacity) : -1;
+            return BMFR_OK;
+        }
+        if (ev) (void)hipEventRecord(ev[1], s);
+        st = hip_status(bmfr::launch_taa(P, s, A.prev_pixel_out, A.tone_out, A.result_out, A.result_prev, A.frame));
+        if (st != BMFR_OK) return st;
+        c->pending_frame = -1;
+        c->pending_prof_slot = -1;
     } else {
         int ix0, ix1, iy0, iy1;
         interior_blocks(c, P, frame_number, &ix0, &ix1, &iy0, &iy1);
@@ -779,12 +806,24 @@ bmfr_status process_part(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in,
 bmfr_status bmfr_process_frame(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in,
                                const float prev_frame_camera_matrix[16], const float pixel_offset[2],
                                int frame_number) {
-    return process_part(c, stream, in, prev_frame_camera_matrix, pixel_offset, frame_number, 2);
+    return process_part(c, stream, in, nullptr, prev_frame_camera_matrix, pixel_offset, frame_number, 2);
+}
+
+bmfr_status bmfr_process_frame_aux(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in, const bmfr_aux_inputs* aux,
+                       const float prev_frame_camera_matrix[16], const float pixel_offset[2], int frame_number) {
+    return process_part(c, stream, in, aux, prev_frame_camera_matrix, pixel_offset, frame_number, 2);
 }
 
 bmfr_status bmfr_process_sequence(bmfr_ctx* c, void* stream, int count, const bmfr_frame_inputs* in,
                                   const float* prev_frame_camera_matrices, const float* pixel_offsets,
                                   int first_frame, float* const* outputs) {
+    return bmfr_process_sequence_aux(c, stream, count, in, nullptr, prev_frame_camera_matrices, pixel_offsets,
+                                     first_frame, outputs);
+}
+
+bmfr_status bmfr_process_sequence_aux(bmfr_ctx* c, void* stream, int count, const bmfr_frame_inputs* in,
+                                      const bmfr_aux_inputs* aux, const float* prev_frame_camera_matrices,
+                                      const float* pixel_offsets, int first_frame, float* const* outputs) {
     if (!c || count <= 0 || !in || !prev_frame_camera_matrices || !pixel_offsets || first_frame < 0)
         return BMFR_ERROR_INVALID_ARGUMENT;
     if (c->pending_frame >= 0) return BMFR_ERROR_INVALID_ARGUMENT;
@@ -796,9 +835,11 @@ bmfr_status bmfr_process_sequence(bmfr_ctx* c, void* stream, int count, const bm
     const size_t out_bytes = c->sizes.region_bytes;
     const bool pipelined = bmfr::fused_supported(c->P);
     if (!pipelined) {  // frame after frame on `stream`
+        for (int i = 0; i < count; ++i)  // a missing plane fails the call before any frame is enqueued
+            if (!aux_planes_ok(c, aux ? &aux[i] : nullptr)) return BMFR_ERROR_INVALID_ARGUMENT;
         for (int i = 0; i < count; ++i) {
-            st = bmfr_process_frame(c, stream, &in[i], prev_frame_camera_matrices + 16 * i, pixel_offsets + 2 * i,
-                                    first_frame + i);
+            st = bmfr_process_frame_aux(c, stream, &in[i], aux ? &aux[i] : nullptr,
+                                        prev_frame_camera_matrices + 16 * i, pixel_offsets + 2 * i, first_frame + i);
             if (st != BMFR_OK) return st;
             if (outputs && outputs[i])
                 if ((st = hip_status(hipMemcpyAsync(outputs[i], c->result[c->cur], out_bytes, hipMemcpyDefault, s))))
@@ -923,13 +964,23 @@ bmfr_status bmfr_process_sequence(bmfr_ctx* c, void* stream, int count, const bm
 bmfr_status bmfr_process_frame_interior(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in,
                                         const float prev_frame_camera_matrix[16], const float pixel_offset[2],
                                         int frame_number) {
-    return process_part(c, stream, in, prev_frame_camera_matrix, pixel_offset, frame_number, 0);
+    return process_part(c, stream, in, nullptr, prev_frame_camera_matrix, pixel_offset, frame_number, 0);
+}
+
+bmfr_status bmfr_process_frame_interior_aux(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in, const bmfr_aux_inputs* aux,
+                       const float prev_frame_camera_matrix[16], const float pixel_offset[2], int frame_number) {
+    return process_part(c, stream, in, aux, prev_frame_camera_matrix, pixel_offset, frame_number, 0);
 }
 
 bmfr_status bmfr_process_frame_border(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in,
                                       const float prev_frame_camera_matrix[16], const float pixel_offset[2],
                                       int frame_number) {
-    return process_part(c, stream, in, prev_frame_camera_matrix, pixel_offset, frame_number, 1);
+    return process_part(c, stream, in, nullptr, prev_frame_camera_matrix, pixel_offset, frame_number, 1);
+}
+
+bmfr_status bmfr_process_frame_border_aux(bmfr_ctx* c, void* stream, const bmfr_frame_inputs* in, const bmfr_aux_inputs* aux,
+                       const float prev_frame_camera_matrix[16], const float pixel_offset[2], int frame_number) {
+    return process_part(c, stream, in, aux, prev_frame_camera_matrix, pixel_offset, frame_number, 1);
 }
 
 // ------------------------------------------------- G-buffer front end ----

@@ -12,11 +12,18 @@ namespace bmfr {
 
 // Features recomputed in f32 from normals/positions, scaled with the block's
 // min/max, dotted with the block's weights (bmfr.cl:703-758).
+// AUX: a feature that names a caller-supplied plane takes the plane's raw
+// value x (no NaN -> 0, no clamp: what bmfr.cl:727-729 does with any
+// feature expression).
+template <bool AUX = false>
 __device__ __forceinline__ f3 weighted_color(const Params& P, const float* __restrict__ w,
-                                             const float* __restrict__ mm, f3 n, f3 p) {
+                                             const float* __restrict__ mm, f3 n, f3 p,
+                                             const AuxVals* x = nullptr) {
     f3 c{0.f, 0.f, 0.f};
     for (int f = 0; f < P.buffers - 3; ++f) {
-        float v = feature_value(P.codes[f], n, p);
+        float v;
+        if constexpr (AUX) v = P.codes[f] >= kFeatAux0 ? aux_value(P.codes[f], *x) : feature_value(P.codes[f], n, p);
+        else v = feature_value(P.codes[f], n, p);
         if (f >= P.not_scaled) v = scale(v, mm[2 * (f - P.not_scaled)], mm[2 * (f - P.not_scaled) + 1]);
         c.x = c.x + w[3 * f] * v;
         c.y = c.y + w[3 * f + 1] * v;
@@ -60,7 +67,23 @@ __global__ __launch_bounds__(256) void k_fitter(Params P, float* __restrict__ we
 // ------------------------------------------- generic-feature fused K1 ----
 // Fallback K1 for feature lists other than the canonical ones (runtime
 // feature codes); the canonical lists use k_fused (bmfr_fused.hip).
-template <int NS, int FS, bool HALF>
+// AUX... = AuxPlanes (instantiated in bmfr_generic_aux_ns*.hip): the list names
+// caller-supplied planes (kFeatAux0..3), a trailing kernel argument.  A named
+// plane's value at the item's (mirrored) pixel is loaded with the item's
+// current-frame loads -- one coalesced dword per lane, independent of the
+// reprojection's gathers.  AUX... empty is the kernel without any of it.
+// Phase 3 (the weighted sum) reads the raw plane values again rather than
+// keeping them (kAuxKeepRaw), by the compiler's resource report: re-read, every
+// aux instantiation has the named one's VGPR count and waves per SIMD (NS = 4,
+// FS = 9, half tmp_data: 184 VGPRs, 2 waves, as named); kept, 16 VGPRs more
+// (200) and a wave per SIMD less at FS = 0, 3, 5, 6.  Neither form adds scratch
+// ("Caller-supplied feature planes").
+constexpr bool kAuxKeepRaw = false;
+// The kernel's trailing argument: none (AUX... empty), or the planes.
+__device__ __forceinline__ const AuxPlanes* aux_arg() { return nullptr; }
+__device__ __forceinline__ const AuxPlanes* aux_arg(const AuxPlanes& a) { return &a; }
+
+template <int NS, int FS, bool HALF, class... AUX>
 __global__ __launch_bounds__(256) void k_fused_block(Params P, NoisyInputs in, Camera cam, int frame,
                                                      const float* __restrict__ albedo,
                                                      const float* __restrict__ acc_prev,
@@ -69,7 +92,9 @@ __global__ __launch_bounds__(256) void k_fused_block(Params P, NoisyInputs in, C
                                                      float2* __restrict__ prev_pixel_out,
                                                      float* __restrict__ acc_out,
                                                      float* __restrict__ tone_out,
-                                                     const float2* __restrict__ prev_pixel_in) {
+                                                     const float2* __restrict__ prev_pixel_in, AUX... planes) {
+    constexpr bool kAux = sizeof...(AUX) > 0;
+    static_assert(sizeof...(AUX) <= 1, "AUX is empty or AuxPlanes");
     constexpr int B = NS + FS + 3;
     __shared__ FitLds<B> L;
     const int t = threadIdx.x, g = blockIdx.x;
@@ -81,14 +106,26 @@ __global__ __launch_bounds__(256) void k_fused_block(Params P, NoisyInputs in, C
     uint32_t lin[kSubs];
     uint32_t flags = 0;  // per s: bit 8s owner, bits 8s+1.. accept(4)
     uint32_t spps = 0;
+    AuxVals raw[kAux ? kSubs : 1];  // kAux: the items' raw plane values
+    const AuxPlanes* aux = aux_arg(planes...);
 #pragma unroll
     for (int s = 0; s < kSubs; ++s) {
         const int r = t + s * kLocal;
         const int gx = bx * kEdge + (r & (kEdge - 1)), gy = by * kEdge + (r >> 5);
+        if constexpr (kAux) {  // the item's pixel as noisy_item forms it; the plane loads go first
+            int px, py;
+            bool owner;
+            item_pixel(P, gx, gy, frame, px, py, owner);
+            const uint32_t l = (uint32_t)(py * P.width + px);
+#pragma unroll
+            for (int k = 0; k < kMaxAux; ++k) raw[s].v[k] = aux->p[k] ? aux->p[k][l] : 0.f;  // wave-uniform
+        }
         const NoisyItem it = noisy_item(P, in, cam, gx, gy, frame, prev_pixel_in);
 #pragma unroll
         for (int f = 0; f < B; ++f) {
-            const float v = design_value(P, f, it);
+            float v;
+            if constexpr (kAux) v = design_value<true>(P, f, it, &raw[s]);
+            else v = design_value(P, f, it);
             a[f][s] = HALF ? round_half(v) : v;
         }
         n_keep[s] = it.n;
@@ -111,7 +148,16 @@ __global__ __launch_bounds__(256) void k_fused_block(Params P, NoisyInputs in, C
     for (int s = 0; s < kSubs; ++s) {
         const uint32_t fl = flags >> (8 * s);
         if (fl & 1u) {
-            const f3 filtered = weighted_color(P, L.weights, L.minmax, n_keep[s], p_keep[s]);
+            f3 filtered;
+            if constexpr (kAux) {
+                if constexpr (!kAuxKeepRaw) {
+#pragma unroll
+                    for (int k = 0; k < kMaxAux; ++k) raw[s].v[k] = aux->p[k] ? aux->p[k][lin[s]] : 0.f;
+                }
+                filtered = weighted_color<true>(P, L.weights, L.minmax, n_keep[s], p_keep[s], &raw[s]);
+            } else {
+                filtered = weighted_color(P, L.weights, L.minmax, n_keep[s], p_keep[s]);
+            }
             const f3 acc = blend_filtered(P, filtered, pfx[s], pfy[s], (uint8_t)((fl >> 1) & 15u),
                                           (uint8_t)(spps >> (8 * s)), acc_prev, frame);
             st3(acc_out, lin[s], acc);
@@ -143,17 +189,37 @@ static hipError_t launch_fused_t(const Params& P, hipStream_t st, const FusedArg
     return hipGetLastError();
 }
 
+template <int NS, int FS>
+static hipError_t launch_fused_aux_t(const Params& P, hipStream_t st, const FusedArgs& A) {
+    const int G = P.blocks_x * P.blocks_y;
+    if (P.half_tmp)
+        hipLaunchKernelGGL((k_fused_block<NS, FS, true, AuxPlanes>), dim3(G), dim3(256), 0, st, P, A.in, A.cam,
+                           A.frame, A.albedo, A.acc_prev, A.noisy_out, A.spp_out, A.prev_pixel_out,
+                           A.acc_out, A.tone_out, A.prev_pixel_in, A.aux);
+    else
+        hipLaunchKernelGGL((k_fused_block<NS, FS, false, AuxPlanes>), dim3(G), dim3(256), 0, st, P, A.in, A.cam,
+                           A.frame, A.albedo, A.acc_prev, A.noisy_out, A.spp_out, A.prev_pixel_out,
+                           A.acc_out, A.tone_out, A.prev_pixel_in, A.aux);
+    return hipGetLastError();
+}
+
 // Entry points per FEATURES_NOT_SCALED: FEATURES_SCALED 0..9 dispatched at
 // run time (defined in bmfr_generic_ns<NS>.hip).
 template <int NS>
 hipError_t launch_fitter_ns(const Params& P, hipStream_t st, float* w, float* mm, void* tmp, int frame);
 template <int NS>
 hipError_t launch_fused_block_ns(const Params& P, hipStream_t st, const FusedArgs& A);
+// The K1 of a list that names caller-supplied planes (defined in
+// bmfr_generic_aux_ns<NS>.hip).
+template <int NS>
+hipError_t launch_fused_block_aux_ns(const Params& P, hipStream_t st, const FusedArgs& A);
 #define BMFR_DECLARE_NS(N)                                                                                  \
     template <>                                                                                             \
     hipError_t launch_fitter_ns<N>(const Params& P, hipStream_t st, float* w, float* mm, void* tmp, int frame); \
     template <>                                                                                             \
-    hipError_t launch_fused_block_ns<N>(const Params& P, hipStream_t st, const FusedArgs& A);
+    hipError_t launch_fused_block_ns<N>(const Params& P, hipStream_t st, const FusedArgs& A);               \
+    template <>                                                                                             \
+    hipError_t launch_fused_block_aux_ns<N>(const Params& P, hipStream_t st, const FusedArgs& A);
 BMFR_DECLARE_NS(1)
 BMFR_DECLARE_NS(2)
 BMFR_DECLARE_NS(3)
@@ -194,6 +260,26 @@ hipError_t launch_fused_block_ns<BMFR_GENERIC_NS>(const Params& P, hipStream_t s
         case 7: return launch_fused_t<NS, 7>(P, st, A);
         case 8: return launch_fused_t<NS, 8>(P, st, A);
         case 9: return launch_fused_t<NS, 9>(P, st, A);
+        default: return hipErrorInvalidValue;
+    }
+}
+#endif
+
+#ifdef BMFR_GENERIC_AUX_NS
+template <>
+hipError_t launch_fused_block_aux_ns<BMFR_GENERIC_AUX_NS>(const Params& P, hipStream_t st, const FusedArgs& A) {
+    constexpr int NS = BMFR_GENERIC_AUX_NS;
+    switch (P.scaled) {
+        case 0: return launch_fused_aux_t<NS, 0>(P, st, A);
+        case 1: return launch_fused_aux_t<NS, 1>(P, st, A);
+        case 2: return launch_fused_aux_t<NS, 2>(P, st, A);
+        case 3: return launch_fused_aux_t<NS, 3>(P, st, A);
+        case 4: return launch_fused_aux_t<NS, 4>(P, st, A);
+        case 5: return launch_fused_aux_t<NS, 5>(P, st, A);
+        case 6: return launch_fused_aux_t<NS, 6>(P, st, A);
+        case 7: return launch_fused_aux_t<NS, 7>(P, st, A);
+        case 8: return launch_fused_aux_t<NS, 8>(P, st, A);
+        case 9: return launch_fused_aux_t<NS, 9>(P, st, A);
         default: return hipErrorInvalidValue;
     }
 }

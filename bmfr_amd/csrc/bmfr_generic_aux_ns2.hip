@@ -1,0 +1,4 @@
+// bmfr_generic_aux_ns2.hip -- the generic-feature K1 of lists that name caller-supplied planes,
+// FEATURES_NOT_SCALED = 2 (bmfr_generic.h).
+#define BMFR_GENERIC_AUX_NS 2
+#include "bmfr_generic.h"

@@ -110,6 +110,23 @@ struct Camera {
     float jx, jy;  // this frame's pixel offset
 };
 
+// Caller-supplied feature planes (bmfr_aux_inputs, feature codes
+// kFeatAux0..3): one f32 per pixel, W x H; null where the feature list does
+// not name the plane.  AuxVals: one item's raw plane values (0 for a plane
+// that is not named).
+struct AuxPlanes {
+    const float* p[kMaxAux];
+};
+struct AuxVals {
+    float v[kMaxAux];
+};
+// The plane value a feature code names (wave-uniform code, compare-and-select
+// chain: a runtime index into registers would go through scratch).
+__device__ __forceinline__ float aux_value(int code, const AuxVals& x) {
+    const int k = code - kFeatAux0;
+    return k == 0 ? x.v[0] : (k == 1 ? x.v[1] : (k == 2 ? x.v[2] : x.v[3]));
+}
+
 // XCD-aware work-group order.  Work-groups are dealt round-robin to the 8
 // XCDs (g % 8), each with its own L2; renumbering so that XCD x gets the
 // contiguous range [x*G/8, (x+1)*G/8) keeps neighbouring blocks -- which
@@ -625,11 +642,17 @@ __device__ __forceinline__ void report_reach(const Params& P, unsigned* reach, i
 
 // tmp_data value of feature f for an item (bmfr.cl:448-473): NaN -> 0, and
 // the +-65504 clamp when the matrix is kept in half.
-__device__ __forceinline__ float design_value(const Params& P, int f, const NoisyItem& it) {
+// AUX (lists that name a caller-supplied plane): such a feature's value is the
+// plane's at the item's pixel (x), treated like any other feature's.
+template <bool AUX = false>
+__device__ __forceinline__ float design_value(const Params& P, int f, const NoisyItem& it,
+                                              const AuxVals* x = nullptr) {
     const int B = P.buffers;
     float v;
-    if (f < B - 3) v = feature_value(P.codes[f], it.n, it.p);
-    else v = f == B - 3 ? it.color.x : (f == B - 2 ? it.color.y : it.color.z);
+    if (f < B - 3) {
+        if constexpr (AUX) v = P.codes[f] >= kFeatAux0 ? aux_value(P.codes[f], *x) : feature_value(P.codes[f], it.n, it.p);
+        else v = feature_value(P.codes[f], it.n, it.p);
+    } else v = f == B - 3 ? it.color.x : (f == B - 2 ? it.color.y : it.color.z);
     if (__builtin_isnan(v)) v = 0.0f;
     if (P.half_tmp) v = fmaxf(fminf(v, 65504.f), -65504.f);
     return v;

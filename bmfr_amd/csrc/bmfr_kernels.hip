@@ -225,7 +225,16 @@ hipError_t launch_fitter(const Params& P, hipStream_t st, float* weights, float*
     }
 }
 
-static hipError_t launch_fused_generic(const Params& P, hipStream_t st, const FusedArgs& A) {
+hipError_t launch_fused_generic(const Params& P, hipStream_t st, const FusedArgs& A) {
+    if (aux_mask(P) != 0) {
+        switch (P.not_scaled) {
+            case 1: return launch_fused_block_aux_ns<1>(P, st, A);
+            case 2: return launch_fused_block_aux_ns<2>(P, st, A);
+            case 3: return launch_fused_block_aux_ns<3>(P, st, A);
+            case 4: return launch_fused_block_aux_ns<4>(P, st, A);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (P.not_scaled) {
         case 1: return launch_fused_block_ns<1>(P, st, A);
         case 2: return launch_fused_block_ns<2>(P, st, A);

@@ -46,6 +46,9 @@ struct FusedArgs {
     // bmfr_frame_inputs.prev_pixel from frame 1 on (null: project with cam): the
     // caller's previous-frame pixel position of every region pixel
     const float2* prev_pixel_in;
+    // bmfr_aux_inputs: the caller-supplied feature planes the context's
+    // list names (null: not named), read by the aux form of the generic-feature K1
+    AuxPlanes aux;
 };
 
 // Kernel arguments of the fused K1 (canonical feature lists).
@@ -107,6 +110,10 @@ hipError_t launch_accumulate_filtered(const Params& P, hipStream_t st, const flo
                                       const float* albedo, float* tone, const uint8_t* spp,
                                       const float* acc_prev, float* acc, int frame);
 hipError_t launch_fused_frame(const Params& P, hipStream_t st, const FusedArgs& A, hipEvent_t mid = nullptr);
+// K1 of the generic-feature path (lists other than the canonical ones,
+// untiled): the aux kernels exactly when the list names a caller-supplied
+// plane (aux_mask).  launch_taa on A.tone_out completes the frame.
+hipError_t launch_fused_generic(const Params& P, hipStream_t st, const FusedArgs& A);
 // The parts of launch_fused_frame (canonical feature lists): the frame's
 // noise table, K1 over the block rectangle of P (bx0, by0, nbx, nby; empty:
 // nothing), K2 over P's output tile.

@@ -15,6 +15,7 @@ enum FeatureCode : int {
     kFeatPx, kFeatPy, kFeatPz,
     kFeatPx2, kFeatPy2, kFeatPz2,
     kFeatPx3, kFeatPy3, kFeatPz3,
+    kFeatAux0, kFeatAux1, kFeatAux2, kFeatAux3,  // caller-supplied planes (bmfr_aux_inputs)
 };
 
 constexpr int kEdge = 32;                 // BLOCK_EDGE_LENGTH
@@ -22,6 +23,7 @@ constexpr int kBlockPixels = kEdge * kEdge;  // BLOCK_PIXELS
 constexpr int kLocal = 256;               // LOCAL_SIZE (fitter work-items)
 constexpr int kSubs = kBlockPixels / kLocal; // rows per fitter work-item
 constexpr int kMaxFeatures = 16;
+constexpr int kMaxAux = 4;                // BMFR_MAX_AUX_FEATURES
 
 struct Params {
     int width, height;            // IMAGE_WIDTH / IMAGE_HEIGHT
@@ -77,6 +79,13 @@ struct Params {
     // (include/bmfr_debug.h bmfr_debug_frame_launches).
     int frame_launches;
 };
+// Bit k: the feature list names caller-supplied plane k (kFeatAux0 + k).
+inline int aux_mask(const Params& P) {
+    int m = 0;
+    for (int f = 0; f < P.not_scaled + P.scaled; ++f)
+        if (P.codes[f] >= kFeatAux0 && P.codes[f] < kFeatAux0 + kMaxAux) m |= 1 << (P.codes[f] - kFeatAux0);
+    return m;
+}
 constexpr int kDefaultMaxPolls = 1 << 20;
 constexpr int kDelayStride = 61, kDelayPhase = 7;
 

@@ -118,6 +118,47 @@ def check_prev_pixel(plane, width: int, height: int, device: int = 0) -> None:
         raise ValueError(f"prev_pixel must live on cuda:{device}, not {plane.device}")
 
 
+def aux_named(cfg: "BmfrConfig") -> tuple:
+    """The aux plane indices (0..3) the configuration's feature lists name."""
+    feats = tuple(cfg.not_scaled) + tuple(cfg.scaled)
+    return tuple(k for k in range(_lib.MAX_AUX_FEATURES) if _lib.FEATURE_AUX0 + k in feats)
+
+
+def check_aux(aux, named, width: int, height: int, device: int = 0) -> tuple:
+    """Raise unless `aux` can be passed as bmfr_aux_inputs.aux (include/bmfr.h)
+    of a context whose feature lists name the planes `named` (aux_named) and
+    whose planes cover width x height pixels on GPU `device`: None, or a
+    sequence of up to four entries, each None or a contiguous float32 tensor of
+    height * width elements there; every named plane must be present.  Runs
+    before any library call, which would read a wrong plane out of bounds.
+    -> the four entries (None where absent)."""
+    if aux is None:
+        aux = ()
+    if isinstance(aux, torch.Tensor) or not hasattr(aux, "__len__"):
+        raise TypeError("aux must be a sequence of up to four tensors or Nones")
+    if len(aux) > _lib.MAX_AUX_FEATURES:
+        raise ValueError(f"aux takes at most {_lib.MAX_AUX_FEATURES} planes, not {len(aux)}")
+    planes = tuple(aux) + (None,) * (_lib.MAX_AUX_FEATURES - len(aux))
+    for k in named:
+        if planes[k] is None:
+            raise ValueError(f"the feature list names FEATURE_AUX{k} but aux[{k}] is missing")
+    for k, t in enumerate(planes):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"aux[{k}] must be a torch tensor or None, not {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"aux[{k}] must be float32, not {t.dtype}")
+        if t.numel() != height * width:
+            raise ValueError(f"aux[{k}] must have {height * width} elements ({height} x {width}), "
+                             f"not {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"aux[{k}] must be contiguous")
+        if t.device.type != "cuda" or (t.device.index or 0) != device:
+            raise ValueError(f"aux[{k}] must live on cuda:{device}, not {t.device}")
+    return planes
+
+
 def _stream(stream) -> int | None:
     s = stream if stream is not None else torch.cuda.current_stream()
     return s.cuda_stream
@@ -149,6 +190,10 @@ class StagePipeline(_Context):
     """The reference frame loop, stage by stage, on reference-layout buffers."""
 
     def __init__(self, cfg: BmfrConfig, device: int = 0):
+        if aux_named(cfg):
+            raise ValueError("StagePipeline cannot run a feature list that names FEATURE_AUX planes: the stage "
+                             "API keeps the reference's kernel signatures, which have no aux argument "
+                             "(bmfr_accumulate_noisy_data / bmfr_weighted_sum: unsupported); use Denoiser")
         super().__init__(cfg, device)
         dev = torch.device("cuda", device)
         W, H = cfg.image_width, cfg.image_height
@@ -230,40 +275,55 @@ class Denoiser(_Context):
     def _check_prev_pixel(self, plane) -> None:
         check_prev_pixel(plane, self.sizes.region_width, self.sizes.region_height, self.device)
 
+    def _check_aux(self, aux):
+        """-> the frame's bmfr_aux_inputs (checked: check_aux)."""
+        planes = check_aux(aux, aux_named(self.cfg), self.sizes.region_width, self.sizes.region_height, self.device)
+        return _lib.AuxInputs((C.c_void_p * _lib.MAX_AUX_FEATURES)(*[_ptr(t) for t in planes]))
+
     def _call(self, fn: str, noisy, normals, positions, albedo, prev_vp, jitter, frame, prev_normals,
-              prev_positions, stream, done: bool, prev_pixel=None) -> None:
+              prev_positions, stream, done: bool, prev_pixel=None, aux=None) -> None:
         self._check_prev_pixel(prev_pixel)
+        aux_c = self._check_aux(aux)
         if frame > 0 and prev_normals is None:
             if self.prev_inputs is None:
                 raise ValueError("frame > 0 needs the previous frame's normals/positions")
             prev_normals, prev_positions = self.prev_inputs
         fi = _lib.FrameInputs(_ptr(noisy), _ptr(normals), _ptr(positions), _ptr(albedo),
                               _ptr(prev_normals), _ptr(prev_positions), _ptr(prev_pixel))
-        check(getattr(self.lib, fn)(self.handle, _stream(stream), C.byref(fi), floats(prev_vp, 16),
-                                    floats(jitter, 2), frame), fn)
+        if aux_named(self.cfg):  # the call with the planes; every other configuration calls what it always did
+            check(getattr(self.lib, fn + "_aux")(self.handle, _stream(stream), C.byref(fi), C.byref(aux_c),
+                                                 floats(prev_vp, 16), floats(jitter, 2), frame), fn + "_aux")
+        else:
+            check(getattr(self.lib, fn)(self.handle, _stream(stream), C.byref(fi), floats(prev_vp, 16),
+                                        floats(jitter, 2), frame), fn)
         if done:
             self.prev_inputs = (normals, positions)
 
     def process_frame(self, noisy, normals, positions, albedo, prev_vp, jitter, frame: int,
-                      prev_normals=None, prev_positions=None, stream=None, prev_pixel=None) -> None:
+                      prev_normals=None, prev_positions=None, stream=None, prev_pixel=None, aux=None) -> None:
         """Run one frame.  prev_normals / prev_positions default to the ones
         passed on the previous call (the reference's Double_buffer halves).
         prev_pixel: optional float32 (H, W, 2) plane of previous-frame pixel
         positions that replaces the projection through prev_vp from frame 1 on
-        (include/bmfr.h bmfr_frame_inputs.prev_pixel; the region for a tile)."""
+        (include/bmfr.h bmfr_frame_inputs.prev_pixel; the region for a tile).
+        aux: a sequence of up to four float32 (H, W) planes or Nones, the
+        values of the features FEATURE_AUX0..3 at this frame's pixels
+        (include/bmfr.h bmfr_aux_inputs); every plane the configuration
+        names must be there."""
         self._call("bmfr_process_frame", noisy, normals, positions, albedo, prev_vp, jitter, frame,
-                   prev_normals, prev_positions, stream, True, prev_pixel)
+                   prev_normals, prev_positions, stream, True, prev_pixel, aux)
 
     def process_sequence(self, frames, cameras, first_frame: int, outputs=None, stream=None) -> None:
         """Frames first_frame .. first_frame+len(frames)-1 in one pipelined call
         (include/bmfr.h bmfr_process_sequence).  frames: dicts with noisy,
         normals, positions, albedo tensors and optionally prev_pixel (a plane
-        as in process_frame, or None) and prev_normals / prev_positions
+        as in process_frame, or None), aux (as in process_frame) and prev_normals / prev_positions
         (default: the frame before's normals / positions); cameras: (prev_vp,
         jitter) per frame; outputs: optional tensors receiving each frame's
         output."""
         n = len(frames)
         arr = (_lib.FrameInputs * n)()
+        aux_arr = (_lib.AuxInputs * n)()
         prev = self.prev_inputs
         for i, fr in enumerate(frames):
             pn, pp = prev if prev is not None else (None, None)
@@ -272,28 +332,35 @@ class Denoiser(_Context):
             self._check_prev_pixel(fr.get("prev_pixel"))
             arr[i] = _lib.FrameInputs(_ptr(fr["noisy"]), _ptr(fr["normals"]), _ptr(fr["positions"]),
                                       _ptr(fr["albedo"]), _ptr(pn), _ptr(pp), _ptr(fr.get("prev_pixel")))
+            aux_arr[i] = self._check_aux(fr.get("aux"))
             prev = (fr["normals"], fr["positions"])
         vps = floats([v for vp, _ in cameras for v in vp], 16 * n)
         offs = floats([v for _, jit in cameras for v in jit], 2 * n)
         outs = None
         if outputs is not None:
             outs = (C.c_void_p * n)(*[_ptr(o) for o in outputs])
-        check(self.lib.bmfr_process_sequence(self.handle, _stream(stream), n, arr, vps, offs, first_frame, outs),
-              "bmfr_process_sequence")
+        if aux_named(self.cfg):
+            check(self.lib.bmfr_process_sequence_aux(self.handle, _stream(stream), n, arr, aux_arr, vps, offs,
+                                                     first_frame, outs), "bmfr_process_sequence_aux")
+        else:
+            check(self.lib.bmfr_process_sequence(self.handle, _stream(stream), n, arr, vps, offs, first_frame, outs),
+                  "bmfr_process_sequence")
         self.prev_inputs = prev
 
     def process_frame_interior(self, noisy, normals, positions, albedo, prev_vp, jitter, frame: int,
-                               prev_normals=None, prev_positions=None, stream=None, prev_pixel=None) -> None:
+                               prev_normals=None, prev_positions=None, stream=None, prev_pixel=None,
+                               aux=None) -> None:
         """First half of a frame (include/bmfr.h): the K1 blocks that need no
         halo; may run while the halo exchange of the previous state is in flight."""
         self._call("bmfr_process_frame_interior", noisy, normals, positions, albedo, prev_vp, jitter, frame,
-                   prev_normals, prev_positions, stream, False, prev_pixel)
+                   prev_normals, prev_positions, stream, False, prev_pixel, aux)
 
     def process_frame_border(self, noisy, normals, positions, albedo, prev_vp, jitter, frame: int,
-                             prev_normals=None, prev_positions=None, stream=None, prev_pixel=None) -> None:
+                             prev_normals=None, prev_positions=None, stream=None, prev_pixel=None,
+                             aux=None) -> None:
         """Second half: the remaining K1 blocks and K2, once the halo is refreshed."""
         self._call("bmfr_process_frame_border", noisy, normals, positions, albedo, prev_vp, jitter, frame,
-                   prev_normals, prev_positions, stream, True, prev_pixel)
+                   prev_normals, prev_positions, stream, True, prev_pixel, aux)
 
     # ---- G-buffer front end (include/bmfr.h bmfr_prepare_frame) ----
     # g key -> (bmfr_gbuffer format field, {tensor dtype: (bmfr_format, elements per pixel)})
@@ -427,7 +494,7 @@ class Denoiser(_Context):
         self.process_frame(cur["noisy"], cur["normals"], cur["positions"], cur["albedo"], prev_vp, jitter, frame,
                            prev_normals=prev_normals if frame > 0 else None,
                            prev_positions=prev_positions if frame > 0 else None, stream=stream,
-                           prev_pixel=prev_pixel)
+                           prev_pixel=prev_pixel, aux=g.get("aux"))
 
     def halo_status(self) -> int:
         """Tiled contexts: waits for the last frame; the largest distance (px)

@@ -33,10 +33,11 @@ extern "C" {
 #endif
 
 #define BMFR_VERSION_MAJOR 0
-#define BMFR_VERSION_MINOR 2
+#define BMFR_VERSION_MINOR 3
 
 #define BMFR_BLOCK_EDGE_LENGTH 32 /* bmfr.cpp:104; other sizes unsupported, as upstream */
 #define BMFR_MAX_FEATURES 16      /* NOT_SCALED + SCALED feature buffers */
+#define BMFR_MAX_AUX_FEATURES 4   /* caller-supplied feature planes (BMFR_FEATURE_AUX0..3) */
 
 typedef enum bmfr_status {
     BMFR_OK = 0,
@@ -53,13 +54,16 @@ typedef enum bmfr_status {
 
 /* Feature buffer monomials.  The reference pastes C expressions into the
  * kernels (NOT_SCALED_FEATURE_BUFFERS / SCALED_FEATURE_BUFFERS, bmfr.cpp:65-77
- * -> FEATURE_BUFFERS, bmfr.cl:448-453,727-729); this ABI names them. */
+ * -> FEATURE_BUFFERS, bmfr.cl:448-453,727-729); this ABI names them.  Any
+ * other expression enters as a plane the caller evaluates:
+ * BMFR_FEATURE_AUXk is bmfr_aux_inputs.aux[k] (see there). */
 typedef enum bmfr_feature {
     BMFR_FEATURE_ONE = 0, /* "1.f" */
     BMFR_FEATURE_NORMAL_X, BMFR_FEATURE_NORMAL_Y, BMFR_FEATURE_NORMAL_Z,
     BMFR_FEATURE_POSITION_X, BMFR_FEATURE_POSITION_Y, BMFR_FEATURE_POSITION_Z,
     BMFR_FEATURE_POSITION_X2, BMFR_FEATURE_POSITION_Y2, BMFR_FEATURE_POSITION_Z2,
     BMFR_FEATURE_POSITION_X3, BMFR_FEATURE_POSITION_Y3, BMFR_FEATURE_POSITION_Z3,
+    BMFR_FEATURE_AUX0, BMFR_FEATURE_AUX1, BMFR_FEATURE_AUX2, BMFR_FEATURE_AUX3, /* 13..16: aux[0..3] */
     BMFR_FEATURE_COUNT_
 } bmfr_feature;
 
@@ -296,6 +300,60 @@ typedef struct bmfr_frame_inputs {  /* float3 planes, or half3 with input_half *
  * vectors, both cases above, and moves prev_positions / prev_normals by one
  * rigid transform per object, on the GPU. */
 
+/* One frame's caller-supplied feature planes, BMFR_FEATURE_AUX0..3.  They
+ * travel beside bmfr_frame_inputs, whose layout is unchanged (seven
+ * pointers), through the *_aux entry points below. */
+typedef struct bmfr_aux_inputs {
+    const float *aux[BMFR_MAX_AUX_FEATURES];
+} bmfr_aux_inputs;
+
+/* aux: feature planes the caller evaluates, for a regression feature the 13
+ * named monomials cannot express -- the reference's FEATURE_BUFFERS takes any
+ * C expression (bmfr.cpp:65-77), e.g. world_position.x*world_position.y --
+ * or a noise-free quantity only the renderer has (linear depth, roughness, an
+ * object id, albedo luminance).  A context whose feature_buffers names
+ * BMFR_FEATURE_AUXk reads aux[k]; an aux code may stand anywhere in the list,
+ * in the not-scaled or the scaled group, more than once, in any order.
+ * Planes the list does not name are ignored, and for a list that names none
+ * the whole struct may be NULL.
+ *
+ * Layout: one f32 per pixel, W x H entries, row stride W; device memory, read
+ * only during the call's kernels; must not overlap any state plane.  The
+ * plane always describes the CURRENT frame: features are evaluated at the
+ * current pixel only, so there is no previous aux plane.
+ *
+ * Semantics: the reference's treatment of any feature expression; only the
+ * source of the value is new.
+ *   - The value of AUXk for a work-item is aux[k][lin], lin the same
+ *     mirrored pixel index at which the work-item reads normals and positions
+ *     (bmfr.cl:310-320).
+ *   - In tmp_data it gets what every feature gets: NaN -> 0 and, with half
+ *     tmp_data, the +-65504 clamp and rounding to half (bmfr.cl:448-473).
+ *   - In the scaled group it is scaled by the block's min / max like a
+ *     position feature (bmfr.cl:510-542); its mins_maxs slot is its position
+ *     in the scaled list.
+ *   - In the weighted sum the raw plane value is used again -- no NaN -> 0,
+ *     no clamp, exactly as a named feature is recomputed at bmfr.cl:727-729
+ *     --, scaled with the block's min / max if the feature is in the scaled
+ *     group, then dotted with the weights in list order.
+ * A plane that holds a named monomial's f32 values (one rounding per
+ * operation: nx, px * px, (px * px) * px) therefore reproduces the named code
+ * bit for bit.
+ *
+ * Passed through bmfr_process_frame_aux, _interior_aux / _border_aux on an
+ * untiled context and bmfr_process_sequence_aux (one bmfr_aux_inputs per
+ * frame): the entry points of the same names with one more argument, equal to
+ * them when it is NULL.  With and without prev_pixel, half and f32 tmp_data,
+ * library_powr 0 and 1.  Every frame entry point, with or without _aux,
+ * returns BMFR_ERROR_INVALID_ARGUMENT, before anything is enqueued, when the
+ * list names AUXk and the frame has no aux[k] (aux NULL, or aux[k] NULL).  A
+ * list that names an aux code is
+ * never canonical: fast_fit is ignored, tiled and input_half contexts are
+ * BMFR_ERROR_UNSUPPORTED, as for any non-canonical list.  The stage API keeps
+ * the reference's signatures: bmfr_accumulate_noisy_data and
+ * bmfr_weighted_sum return BMFR_ERROR_UNSUPPORTED for such a context;
+ * bmfr_fitter, which reads only tmp_data, works. */
+
 /* prev_frame_camera_matrix: column-major view-projection of frame-1
  * (camera_matrices[max(frame-1,0)], bmfr.cpp:440-442); pixel_offset: the
  * frame's jitter (pixel_offsets[frame], bmfr.cpp:443-444).  frame_number 0
@@ -336,6 +394,22 @@ bmfr_status bmfr_process_frame_border(bmfr_ctx *ctx, void *stream, const bmfr_fr
 bmfr_status bmfr_process_sequence(bmfr_ctx *ctx, void *stream, int count, const bmfr_frame_inputs *in,
     const float *prev_frame_camera_matrices, const float *pixel_offsets, int first_frame,
     float *const *outputs);
+
+/* The four entry points above with the frame's caller-supplied feature planes
+ * (bmfr_aux_inputs, "aux" above; nullable: then they are the calls above).
+ * bmfr_process_sequence_aux: aux[i] holds frame first_frame+i's planes. */
+bmfr_status bmfr_process_frame_aux(bmfr_ctx *ctx, void *stream, const bmfr_frame_inputs *in,
+    const bmfr_aux_inputs *aux, const float prev_frame_camera_matrix[16], const float pixel_offset[2],
+    int frame_number);
+bmfr_status bmfr_process_frame_interior_aux(bmfr_ctx *ctx, void *stream, const bmfr_frame_inputs *in,
+    const bmfr_aux_inputs *aux, const float prev_frame_camera_matrix[16], const float pixel_offset[2],
+    int frame_number);
+bmfr_status bmfr_process_frame_border_aux(bmfr_ctx *ctx, void *stream, const bmfr_frame_inputs *in,
+    const bmfr_aux_inputs *aux, const float prev_frame_camera_matrix[16], const float pixel_offset[2],
+    int frame_number);
+bmfr_status bmfr_process_sequence_aux(bmfr_ctx *ctx, void *stream, int count, const bmfr_frame_inputs *in,
+    const bmfr_aux_inputs *aux, const float *prev_frame_camera_matrices, const float *pixel_offsets,
+    int first_frame, float *const *outputs);
 
 /* ---- G-buffer front end: from a renderer's buffers to bmfr_frame_inputs ----
  * (no reference counterpart: the reference reads a dataset that already holds
