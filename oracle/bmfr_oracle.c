@@ -329,33 +329,40 @@ static float tree_sum(const float s_in[LSIZE]) {
     return r;
 }
 
+/* fmax / fmin as the GPU evaluates them (v_max_f32 / v_min_f32 order the
+ * zeros, -0 < +0; C's fmaxf / fminf may return either, and x86's depends on the
+ * operand order).  A scaled normal component is +-0 over whole walls, and the
+ * block's min / max are recorded in mins_maxs bit for bit. */
+static float max_f(float a, float b) { return a == b ? (signbit(a) ? b : a) : fmaxf(a, b); }
+static float min_f(float a, float b) { return a == b ? (signbit(a) ? a : b) : fminf(a, b); }
+
 static float tree_max(const float s_in[LSIZE]) {   /* bmfr.cl:68-87 */
     float s[64];
     for (int t = 0; t < 64; ++t)
-        s[t] = fmaxf(fmaxf(fmaxf(s_in[t], s_in[t + 64]), s_in[t + 128]), s_in[t + 192]);
+        s[t] = max_f(max_f(max_f(s_in[t], s_in[t + 64]), s_in[t + 128]), s_in[t + 192]);
     float e[8];
     for (int t = 0; t < 8; ++t) {
         float a = s[t];
-        for (int k = 1; k < 8; ++k) a = fmaxf(a, s[t + 8 * k]);
+        for (int k = 1; k < 8; ++k) a = max_f(a, s[t + 8 * k]);
         e[t] = a;
     }
     float r = e[0];
-    for (int t = 1; t < 8; ++t) r = fmaxf(r, e[t]);
+    for (int t = 1; t < 8; ++t) r = max_f(r, e[t]);
     return r;
 }
 
 static float tree_min(const float s_in[LSIZE]) {   /* bmfr.cl:46-66 */
     float s[64];
     for (int t = 0; t < 64; ++t)
-        s[t] = fminf(fminf(fminf(s_in[t], s_in[t + 64]), s_in[t + 128]), s_in[t + 192]);
+        s[t] = min_f(min_f(min_f(s_in[t], s_in[t + 64]), s_in[t + 128]), s_in[t + 192]);
     float e[8];
     for (int t = 0; t < 8; ++t) {
         float a = s[t];
-        for (int k = 1; k < 8; ++k) a = fminf(a, s[t + 8 * k]);
+        for (int k = 1; k < 8; ++k) a = min_f(a, s[t + 8 * k]);
         e[t] = a;
     }
     float r = e[0];
-    for (int t = 1; t < 8; ++t) r = fminf(r, e[t]);
+    for (int t = 1; t < 8; ++t) r = min_f(r, e[t]);
     return r;
 }
 
@@ -407,8 +414,8 @@ static void fit_block(const oracle_cfg *c, float *weights, float *mins_maxs, voi
             float mx = -INFINITY, mn = INFINITY;
             for (int s = 0; s < SUBS; ++s) {
                 const float v = A[f][t + s * LSIZE];
-                mx = fmaxf(v, mx);
-                mn = fminf(v, mn);
+                mx = max_f(v, mx);
+                mn = min_f(v, mn);
             }
             pmax[t] = mx; pmin[t] = mn;
         }

@@ -25,7 +25,17 @@ import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from ref_configs import FULL_REF_CONFIGS, KNOB_REF_CONFIGS, REF_CONFIGS, REF_MODES  # noqa: E402
+from ref_configs import (FULL_REF_CONFIGS, KNOB_REF_CONFIGS, REF_CONFIGS, REF_MODES,  # noqa: E402
+                         SHAPE_REF_CONFIGS)
+
+# (configurations, the modes they are compiled in).  The shape sweep is compared
+# bit for bit only, so it gets the strict build alone.
+BUILDS = (
+    (REF_CONFIGS, ("strict", "default")),
+    (FULL_REF_CONFIGS, ("strict", "default")),
+    (KNOB_REF_CONFIGS, ("strict", "default")),
+    (SHAPE_REF_CONFIGS, ("strict",)),
+)
 
 CLANG = "/opt/rocm/lib/llvm/bin/clang"
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
@@ -54,25 +64,36 @@ def kernel_layouts(hsaco: str) -> dict:
     return out
 
 
+def same_options(meta: str, options: list) -> bool:
+    """The object on disk was compiled with these options (a configuration
+    whose lists or parameters changed is compiled again)."""
+    try:
+        with open(meta) as f:
+            return json.load(f).get("options") == options
+    except (OSError, ValueError):
+        return False
+
+
 def build(ref_dir: str, force: bool = False) -> list:
     os.makedirs(OUT, exist_ok=True)
     src = os.path.join(HERE, "ref_wrappers.cl")
     built = []
-    for name, cfg in {**REF_CONFIGS, **FULL_REF_CONFIGS, **KNOB_REF_CONFIGS}.items():
-        for mode, flags in REF_MODES.items():
+    for name, cfg, modes in [(n, c, m) for d, m in BUILDS for n, c in d.items()]:
+        for mode in modes:
+            flags = REF_MODES[mode]
             hsaco = os.path.join(OUT, f"{name}_{mode}.hsaco")
             meta = os.path.join(OUT, f"{name}_{mode}.json")
+            options = [*flags, *cfg.ref_build_options()]
             if not force and os.path.exists(hsaco) and os.path.exists(meta) and \
-                    os.path.getmtime(hsaco) >= os.path.getmtime(src):
+                    os.path.getmtime(hsaco) >= os.path.getmtime(src) and same_options(meta, options):
                 built.append(hsaco)
                 continue
             cmd = [CLANG, "-x", "cl", "-cl-std=CL1.2", "-target", "amdgcn-amd-amdhsa",
                    "-mcpu=gfx950", "-O3", "-Xclang", "-finclude-default-header",
-                   "-Wno-everything", "-I", ref_dir, *flags, *cfg.ref_build_options(),
-                   src, "-o", hsaco]
+                   "-Wno-everything", "-I", ref_dir, *options, src, "-o", hsaco]
             subprocess.run(cmd, check=True)
             with open(meta, "w") as f:
-                json.dump({"config": name, "mode": mode, "flags": flags,
+                json.dump({"config": name, "mode": mode, "flags": flags, "options": options,
                            "kernels": kernel_layouts(hsaco)}, f, indent=1)
             built.append(hsaco)
     return built

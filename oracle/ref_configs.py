@@ -204,6 +204,75 @@ def knob_set_of(name: str) -> str:
     return name.split("_")[1]
 
 
+# The shape sweep (tests/test_shapes_cpu.py, tests/test_gpu_shapes.py): one
+# configuration per (FEATURES_NOT_SCALED, FEATURES_SCALED, tmp_data precision)
+# the library instantiates a generic-count kernel for -- NS 1..4, FS 0..9, both
+# precisions, 80 in all --, named g_n<NS>s<FS>_<h|f>.  80x48: both axes padded
+# (96x64 workset, 4x3 block grid with the margins).  3 frames: reprojection, two
+# block offsets, the noise seed's frame term.  Content: scene "rand" of
+# tests/scenes_np.py with seed SHAPE_SEED.
+#
+# Lists: position 0 is code 0 (1.f), as in every list the reference ships; the
+# other NS + FS - 1 positions are codes 1..12 without repetition, by a rotation:
+# position i holds 1 + (start + 5 i) mod 12, start = (7 FS + 4 NS + extra) mod
+# 12, extra = SHAPE_ROTATION.get((NS, FS), 0).  A step of 5 never gives 1, 2, 3
+# in a row, so no list is a canonical one.  Both precisions take the same list.
+SHAPE_SIZE = (80, 48)
+SHAPE_FRAMES = 3
+SHAPE_SCENE = "rand"
+SHAPE_SEED = 7
+SHAPE_NS = (1, 2, 3, 4)
+SHAPE_FS = tuple(range(10))
+# (NS, FS) -> another rotation, for a list on which the CPU oracle's records
+# are not all finite (tests/test_shapes_cpu.py); none needed so far
+SHAPE_ROTATION = {}
+
+
+def shape_lists(ns: int, fs: int):
+    """(not_scaled, scaled) of the sweep's shape (ns, fs)."""
+    start = (7 * fs + 4 * ns + SHAPE_ROTATION.get((ns, fs), 0)) % 12
+    rest = tuple(1 + (start + 5 * i) % 12 for i in range(ns + fs - 1))
+    return (0,) + rest[:ns - 1], rest[ns - 1:]
+
+
+def shape_name(ns: int, fs: int, half_tmp: int) -> str:
+    return f"g_n{ns}s{fs}_{'h' if half_tmp else 'f'}"
+
+
+def shape_of(name: str):
+    """(NS, FS, half_tmp) of a sweep name, the odd lists included."""
+    rc = SHAPE_REF_CONFIGS[name]
+    return len(rc.not_scaled), len(rc.scaled), rc.half_tmp
+
+
+# Lists the rule does not give, at (3, 5) in both precisions: no constant at
+# all; the constant in the scaled group (a constant column's max - min is 0:
+# the |max - min| <= 1 arm of scale(), bmfr.cl:200-205, leaves a zero column);
+# one code (position.x) in both groups.  Position 0 of the first two is a
+# position: the first column is the one the fit adds no noise to (bmfr.cl:623-626),
+# and a normal component vanishes on whole blocks of an axis-aligned wall, which
+# makes the first Householder step 0 / 0 in the reference itself.
+SHAPE_ODD_LISTS = {
+    "noconst": ((6, 2, 10), (4, 8, 12, 1, 5)),
+    "cscaled": ((5, 1, 3), (7, 0, 9, 11, 2)),
+    "twice": ((0, 4, 2), (4, 6, 8, 10, 12)),
+}
+
+
+def _shape_config(name, lists, half_tmp) -> RefConfig:
+    return RefConfig(name, *SHAPE_SIZE, not_scaled=lists[0], scaled=lists[1], half_tmp=half_tmp,
+                     frames=SHAPE_FRAMES, seed=SHAPE_SEED)
+
+
+SHAPE_REF_CONFIGS = {
+    c.name: c
+    for c in [_shape_config(shape_name(ns, fs, h), shape_lists(ns, fs), h)
+              for h in (1, 0) for ns in SHAPE_NS for fs in SHAPE_FS] +
+             [_shape_config(f"{shape_name(3, 5, h)}_{odd}", lists, h)
+              for h in (1, 0) for odd, lists in SHAPE_ODD_LISTS.items()]
+}
+
+
 # Build modes of the reference: "strict" fixes the arithmetic OpenCL leaves to
 # the implementation (no contraction, correctly rounded / and sqrt) and is the
 # one the oracle is pinned to bit-for-bit; "default" is what bmfr.cpp's

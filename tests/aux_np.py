@@ -58,6 +58,7 @@ def object_id(n, p, a, W, H):
 
 
 PLANES = {
+    "one": lambda n, p, a, W, H: np.ones(n.shape[0], f32),
     "nx": lambda n, p, a, W, H: _col(n, 0),
     "ny": lambda n, p, a, W, H: _col(n, 1),
     "nz": lambda n, p, a, W, H: _col(n, 2),
@@ -77,7 +78,7 @@ PLANES = {
     "objid": object_id,
 }
 # the named code a monomial plane stands for
-CODE_OF = {"nx": 1, "ny": 2, "nz": 3, "px": 4, "py": 5, "pz": 6, "px2": 7, "py2": 8, "pz2": 9, "px3": 10, "py3": 11,
+CODE_OF = {"one": 0, "nx": 1, "ny": 2, "nz": 3, "px": 4, "py": 5, "pz": 6, "px2": 7, "py2": 8, "pz2": 9, "px3": 10, "py3": 11,
            "pz3": 12}
 
 
