@@ -88,6 +88,10 @@ class AuxInputs(C.Structure):
 
 # bmfr_format: element formats of G-buffer planes
 FORMAT_NONE, FORMAT_F32X3, FORMAT_F16X4, FORMAT_UNORM8X4, FORMAT_OCT_SNORM16X2, FORMAT_F32X2, FORMAT_F16X2 = range(7)
+# output surfaces only (bmfr_resolve_output)
+FORMAT_UNORM8X3, FORMAT_UNORM10X3A2 = 7, 8
+# bmfr_resolve_source
+RESOLVE_OUTPUT, RESOLVE_HDR = 0, 1
 
 
 class GBuffer(C.Structure):
@@ -109,6 +113,15 @@ class Prepared(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("noisy", "normals", "positions", "albedo", "prev_pixel", "prev_positions_moved",
                  "prev_normals_moved")]
+
+
+class Surface(C.Structure):
+    """bmfr_surface: the destination of bmfr_resolve_output (include/bmfr.h)."""
+    _fields_ = [
+        ("data", C.c_void_p), ("format", C.c_int), ("pitch", C.c_size_t),
+        ("width", C.c_int), ("height", C.c_int), ("origin_x", C.c_int), ("origin_y", C.c_int),
+        ("flip_y", C.c_int), ("bgr", C.c_int), ("alpha", C.c_float),
+    ]
 
 
 class StateView(C.Structure):
@@ -143,6 +156,8 @@ SIGNATURES = {
     "bmfr_process_frame_interior": (_I, [_P, _P, C.POINTER(FrameInputs), _F16, _F2, _I]),
     "bmfr_gbuffer_default": (None, [C.POINTER(GBuffer)]),
     "bmfr_prepare_frame": (_I, [_P, _P, C.POINTER(GBuffer), C.POINTER(Prepared), _F2]),
+    "bmfr_surface_default": (None, [C.POINTER(Surface)]),
+    "bmfr_resolve_output": (_I, [_P, _P, _I, _P, C.POINTER(Surface)]),
     "bmfr_halo_copy": (_I, [_P, _P, C.POINTER(C.c_int), _I, _P, _I, C.POINTER(C.c_size_t)]),
     "bmfr_halo_need": (_I, [C.POINTER(Config), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmfr_process_sequence": (_I, [_P, _P, _I, C.POINTER(FrameInputs), _F16, _F2, _I, C.POINTER(_P)]),

@@ -15,6 +15,7 @@
 #include "../../include/bmfr_debug.h"
 #include "bmfr_launch.h"
 #include "bmfr_prepare.h"
+#include "bmfr_resolve.h"
 
 using bmfr::Params;
 
@@ -1064,6 +1065,70 @@ bmfr_status bmfr_prepare_frame(bmfr_ctx* c, void* stream, const bmfr_gbuffer* g,
     a.n = (uint32_t)c->sizes.region_width * (uint32_t)c->sizes.region_height;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_prepare(a, c->cfg.input_half != 0, static_cast<hipStream_t>(stream)));
+}
+
+void bmfr_surface_default(bmfr_surface* s) {
+    if (!s) return;
+    std::memset(s, 0, sizeof *s);
+    s->alpha = 1.0f;
+}
+
+namespace {
+
+// dst, source and albedo alone (no context, no device).
+bmfr_status check_resolve_args(int source, const void* albedo, const bmfr_surface* d) {
+    if (!d || !d->data || d->width <= 0 || d->height <= 0) return BMFR_ERROR_INVALID_ARGUMENT;
+    size_t bpp, align;
+    switch (d->format) {
+    case BMFR_FORMAT_F32X3: bpp = 12, align = 4; break;
+    case BMFR_FORMAT_F16X4: bpp = 8, align = 8; break;
+    case BMFR_FORMAT_UNORM8X4:
+    case BMFR_FORMAT_UNORM10X3A2: bpp = 4, align = 4; break;
+    case BMFR_FORMAT_UNORM8X3: bpp = 3, align = 1; break;
+    default: return BMFR_ERROR_UNSUPPORTED;
+    }
+    if (d->pitch < (size_t)d->width * bpp || d->pitch % align != 0 || reinterpret_cast<uintptr_t>(d->data) % align != 0 ||
+        d->pitch > (size_t)1 << 31)  // row * pitch stays inside 64 bits
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    if (source != BMFR_RESOLVE_OUTPUT && source != BMFR_RESOLVE_HDR) return BMFR_ERROR_INVALID_ARGUMENT;
+    if (source == BMFR_RESOLVE_HDR && !albedo) return BMFR_ERROR_INVALID_ARGUMENT;
+    return BMFR_OK;
+}
+
+}  // namespace
+
+bmfr_status bmfr_resolve_output(bmfr_ctx* c, void* stream, int source, const void* albedo, const bmfr_surface* d) {
+    const bmfr_status st = check_resolve_args(source, albedo, d);
+    if (st != BMFR_OK) return st;
+    if (!c || !c->has_frame || c->pending_frame >= 0) return BMFR_ERROR_INVALID_ARGUMENT;
+    const bmfr_config& g = c->cfg;
+    const bmfr_sizes& z = c->sizes;
+    const bool tiled = is_tiled(&g);
+    const int tx = tiled ? g.tile_x : 0, ty = tiled ? g.tile_y : 0;
+    const int tw = tiled ? g.tile_width : g.image_width, th = tiled ? g.tile_height : g.image_height;
+    // the tile's rectangle in the surface (64-bit: origins are the caller's)
+    const long long x0 = (long long)d->origin_x + tx;
+    const long long y0 = (long long)d->origin_y + (d->flip_y ? g.image_height - ty - th : ty);
+    if (x0 < 0 || y0 < 0 || x0 + tw > d->width || y0 + th > d->height) return BMFR_ERROR_INVALID_ARGUMENT;
+    bmfr::ResolveArgs a{};
+    a.src = source == BMFR_RESOLVE_HDR ? c->acc[c->cur] : c->result[c->cur];
+    a.albedo = source == BMFR_RESOLVE_HDR ? albedo : nullptr;
+    a.dst = d->data;
+    a.pitch = (long long)d->pitch;
+    a.alpha = d->alpha;
+    a.format = d->format;
+    a.albedo_half = g.input_half != 0;
+    a.bgr = d->bgr != 0;
+    a.rw = z.region_width;
+    a.sx0 = tx - z.region_x;
+    a.sy0 = ty - z.region_y;
+    a.tw = tw;
+    a.th = th;
+    a.dx0 = (int)x0;
+    a.dy0 = (int)(d->flip_y ? y0 + th - 1 : y0);  // tile row 0 is the rectangle's last row when flipped
+    a.dy_step = d->flip_y ? -1 : 1;
+    DeviceGuard guard(c->device);
+    return hip_status(bmfr::launch_resolve(a, as_stream(stream)));
 }
 
 bmfr_status bmfr_halo_copy(bmfr_ctx* c, void* stream, const int* rects, int n, void* buffer, int unpack,

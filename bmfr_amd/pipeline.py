@@ -549,6 +549,59 @@ class Denoiser(_Context):
         hip_memcpy_d2d(dst.data_ptr(), self.output_ptr(), self.sizes.region_bytes, stream)
         return dst
 
+    # ---- Output back end (include/bmfr.h bmfr_resolve_output) ----
+    # (dst dtype, channels; None = a 2-D tensor) -> bmfr_format
+    _SURFACE_FORMATS = {(torch.uint8, 4): _lib.FORMAT_UNORM8X4, (torch.uint8, 3): _lib.FORMAT_UNORM8X3,
+                        (torch.float16, 4): _lib.FORMAT_F16X4, (torch.float32, 3): _lib.FORMAT_F32X3,
+                        (torch.int32, None): _lib.FORMAT_UNORM10X3A2}
+    _RESOLVE_SOURCES = {"output": _lib.RESOLVE_OUTPUT, "hdr": _lib.RESOLVE_HDR}
+
+    def resolve_args(self, dst, source="output", albedo=None, origin=(0, 0), flip_y=False, bgr=False, alpha=1.0):
+        """The checked arguments of bmfr_resolve_output -> (source code, albedo
+        pointer, bmfr_surface); a caller that repeats a call keeps them.  Runs
+        before the call, which would write a wrong surface out of bounds."""
+        if not isinstance(dst, torch.Tensor):
+            raise TypeError(f"dst must be a torch tensor, not {type(dst).__name__}")
+        channels = dst.shape[2] if dst.dim() == 3 else None
+        fmt = self._SURFACE_FORMATS.get((dst.dtype, channels)) if dst.dim() in (2, 3) else None
+        if fmt is None:
+            raise TypeError("dst must be (rows, cols, 4) or (rows, cols, 3) uint8, (rows, cols, 4) float16, "
+                            f"(rows, cols, 3) float32 or (rows, cols) int32, not {tuple(dst.shape)} {dst.dtype}")
+        inner = (channels, 1) if channels else (1,)
+        if dst.numel() == 0 or tuple(dst.stride()[1:]) != inner or dst.stride(0) < dst.shape[1] * (channels or 1):
+            raise ValueError(f"dst must have packed pixels and rows that do not overlap (strides {dst.stride()}); "
+                             "only its row stride is free")
+        if source not in self._RESOLVE_SOURCES:
+            raise ValueError(f"source must be one of {sorted(self._RESOLVE_SOURCES)}, not {source!r}")
+        if source == "hdr":
+            if albedo is None:
+                raise ValueError("source 'hdr' needs the frame's albedo plane")
+            self._check_plane("albedo", albedo, {torch.float16 if self.cfg.input_half else torch.float32: (None, 3)})
+        if dst.device.type != "cuda" or (dst.device.index or 0) != self.device:
+            raise ValueError(f"dst must live on cuda:{self.device}, not {dst.device}")
+        s = _lib.Surface()
+        self.lib.bmfr_surface_default(C.byref(s))
+        s.data, s.format, s.pitch = dst.data_ptr(), fmt, dst.stride(0) * dst.element_size()
+        s.width, s.height = dst.shape[1], dst.shape[0]
+        s.origin_x, s.origin_y = int(origin[0]), int(origin[1])
+        s.flip_y, s.bgr, s.alpha = int(bool(flip_y)), int(bool(bgr)), float(alpha)
+        return self._RESOLVE_SOURCES[source], (_ptr(albedo) if source == "hdr" else None), s
+
+    def resolve(self, dst, source="output", albedo=None, origin=(0, 0), flip_y=False, bgr=False, alpha=1.0,
+                stream=None):
+        """bmfr_resolve_output: the last frame's tile (never its halo) into the
+        surface `dst` in one kernel launch.  dst: a CUDA tensor (rows, cols, C)
+        -- uint8 with C = 4 (RGBA8) or 3 (RGB8), float16 with C = 4 (RGBA16F),
+        float32 with C = 3 -- or (rows, cols) int32 (R10G10B10A2); its row
+        stride is the pitch, so a row- or column-sliced view of a larger tensor
+        works.  source: "output" (the TAA result, display-referred) or "hdr"
+        (albedo * filtered_accumulated, linear; albedo = the frame's albedo
+        plane as given to process_frame).  origin: the surface pixel of frame
+        pixel (0, 0), negative for a tile-sized surface.  -> dst."""
+        src, alb, s = self.resolve_args(dst, source, albedo, origin, flip_y, bgr, alpha)
+        check(self.lib.bmfr_resolve_output(self.handle, _stream(stream), src, alb, C.byref(s)), "bmfr_resolve_output")
+        return dst
+
     @property
     def region(self):
         """(x, y, width, height) of the image pixels this context's planes hold."""

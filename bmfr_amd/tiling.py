@@ -401,6 +401,19 @@ def region_slice(plane, width: int, height: int, region: Rect):
     return plane.reshape(height, width, -1)[y:y + h, x:x + w].contiguous()
 
 
+def resolve_tiled(denoisers, dst, albedo=None, **kw) -> None:
+    """Every tile context of an in-process grid resolves its tile into the same
+    whole-frame surface `dst` (Denoiser.resolve; kw: source, origin, flip_y,
+    bgr, alpha, stream): the compose step of the tiled path, one launch per
+    tile.  albedo (source "hdr"): the full-frame albedo plane, cut to each
+    context's region like the planes of process_frame_tiled."""
+    for d in denoisers:
+        cut = None
+        if albedo is not None:
+            cut = region_slice(albedo, d.cfg.image_width, d.cfg.image_height, d.region).reshape(-1)
+        d.resolve(dst, albedo=cut, **kw)
+
+
 def process_frame_tiled(denoisers, frame_planes, prev_vp, jitter, frame: int, exchange=None, prev_planes=None,
                         prev_pixel=None) -> None:
     """One frame on every rank of an in-process tile grid: full-frame planes

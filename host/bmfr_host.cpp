@@ -77,6 +77,10 @@ struct Options {
     // plane (bmfr_state_view.prev_frame_pixel / bmfr_frame_inputs.prev_pixel)
     // as PREFIXNN.exr, FLOAT, R = x, G = y, B = 0
     std::string dump_prev_pixel, prev_pixel;
+    // --device-quantize: each context resolves its output into an 8-bit RGB
+    // device surface (bmfr_resolve_output, BMFR_FORMAT_UNORM8X3); the host reads
+    // back 3 bytes per pixel instead of 12 and writes them as they are
+    bool device_quantize = false;
 };
 
 void usage() {
@@ -105,7 +109,9 @@ void usage() {
         "  --dump-prev-pixel PREFIX  write each frame's previous-frame pixel positions (the plane K1\n"
         "                         stores) as PREFIXNN.exr: FLOAT, R = x, G = y, B = 0\n"
         "  --prev-pixel PREFIX    read such files and pass them as bmfr_frame_inputs.prev_pixel from\n"
-        "                         frame 1 on, instead of projecting with the camera matrices\n");
+        "                         frame 1 on, instead of projecting with the camera matrices\n"
+        "  --device-quantize      PNG output only: quantise on the GPU (bmfr_resolve_output into an 8-bit RGB\n"
+        "                         surface) and read back 3 bytes per pixel instead of 12; the same files\n");
 }
 
 bool parse_args(int argc, char** argv, Options& o) {
@@ -146,6 +152,7 @@ bool parse_args(int argc, char** argv, Options& o) {
         else if (a == "--fast-fit") o.fast_fit = 1;
         else if (a == "--dump-prev-pixel") o.dump_prev_pixel = next("a prefix");
         else if (a == "--prev-pixel") o.prev_pixel = next("a prefix");
+        else if (a == "--device-quantize") o.device_quantize = true;
         else if (a == "-h" || a == "--help") {
             usage();
             std::exit(0);
@@ -156,6 +163,10 @@ bool parse_args(int argc, char** argv, Options& o) {
         }
     }
     if (o.camera.empty()) o.camera = o.input + "/camera_matrices.h";
+    if (o.device_quantize && (o.exr || !o.psnr.empty())) {
+        std::fprintf(stderr, "--device-quantize writes PNG files only (not with --exr or --psnr)\n");
+        return false;
+    }
     return true;
 }
 
@@ -331,7 +342,8 @@ void split(int n, int parts, int i, int& a, int& b) {
 // host frame.  Host frames are full-size; a tile uploads its region.
 int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, const std::vector<std::vector<float>>& noisy,
               const std::vector<std::vector<float>>& normals, const std::vector<std::vector<float>>& positions,
-              const std::vector<std::vector<float>>& albedos, std::vector<std::vector<float>>& out) {
+              const std::vector<std::vector<float>>& albedos, std::vector<std::vector<float>>& out,
+              std::vector<std::vector<uint8_t>>& out8) {
     const int W = o.width, H = o.height, F = o.frames, T = o.tiles_x * o.tiles_y;
     if (o.gpus != 1 && o.gpus != T) {
         std::fprintf(stderr, "--gpus must be 1 or the number of tiles (%d)\n", T);
@@ -353,6 +365,7 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
         hipEvent_t joined = nullptr;  // one-GPU runs: the stream join around the exchange
         float* in[2][4] = {};  // current / previous region planes: noisy, normal, position, albedo
         bmfr_exchange* x = nullptr;
+        uint8_t* quantized = nullptr;  // --device-quantize: the tile's 8-bit RGB surface
     };
     std::vector<Tile> t(T);
     std::vector<bmfr_comm*> comms(T, nullptr);
@@ -376,6 +389,7 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
         for (auto& s : q.in)
             for (auto& p : s) HIP_CHECK(hipMalloc(&p, q.sz.region_bytes));
         BMFR_CHECK(bmfr_exchange_create(q.ctx, &q.cfg, tiles.data(), T, r, comms[r], &q.x));
+        if (o.device_quantize) HIP_CHECK(hipMalloc(&q.quantized, (size_t)q.cfg.tile_width * q.cfg.tile_height * 3));
     }
     std::printf("Processing %d frames (%dx%d) as %dx%d tiles, halo %d px, on %d GPU(s).\n", F, W, H, o.tiles_x,
                 o.tiles_y, o.tile_halo, o.gpus);
@@ -436,6 +450,16 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
             const float* res = bmfr_output(q.ctx);
             const int tx = tiles[4 * r], ty = tiles[4 * r + 1], tw = tiles[4 * r + 2], th = tiles[4 * r + 3];
             HIP_CHECK(hipSetDevice(q.device));
+            if (o.device_quantize) {  // a tile-sized surface: frame pixel (0, 0) lies at -tile
+                bmfr_surface s;
+                bmfr_surface_default(&s);
+                s.data = q.quantized, s.format = BMFR_FORMAT_UNORM8X3, s.pitch = (size_t)tw * 3;
+                s.width = tw, s.height = th, s.origin_x = -tx, s.origin_y = -ty;
+                BMFR_CHECK(bmfr_resolve_output(q.ctx, q.stream, BMFR_RESOLVE_OUTPUT, nullptr, &s));
+                HIP_CHECK(hipMemcpy2DAsync(out8[f].data() + ((size_t)ty * W + tx) * 3, (size_t)W * 3, q.quantized,
+                                           (size_t)tw * 3, (size_t)tw * 3, th, hipMemcpyDeviceToHost, q.stream));
+                continue;
+            }
             HIP_CHECK(hipMemcpy2DAsync(out[f].data() + ((size_t)ty * W + tx) * 3, (size_t)W * 12,
                                        res + ((size_t)(ty - z.region_y) * z.region_width + (tx - z.region_x)) * 3,
                                        (size_t)z.region_width * 12, (size_t)tw * 12, th, hipMemcpyDeviceToHost,
@@ -464,6 +488,7 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
         Tile& q = t[r];
         HIP_CHECK(hipSetDevice(q.device));
         bmfr_exchange_destroy(q.x);
+        (void)hipFree(q.quantized);
         for (auto& s : q.in)
             for (auto& p : s) (void)hipFree(p);
         (void)hipStreamDestroy(q.stream);
@@ -552,6 +577,8 @@ int run(const Options& o) {
     // ---- Loading input data (bmfr.cpp:254-307) ----
     std::printf("Loading input data.\n");
     std::vector<std::vector<float>> albedos(F), normals(F), positions(F), noisy(F), out(F);
+    std::vector<std::vector<uint8_t>> out8(o.device_quantize ? F : 0);  // --device-quantize: the frames as read back
+    for (auto& v : out8) v.resize(plane);
     bool error = false;
 #pragma omp parallel for
     for (int f = 0; f < F; ++f) {
@@ -605,7 +632,7 @@ int run(const Options& o) {
     }
     for (auto& v : pp_out) v.resize(px_count * 2);
     if (tiled) {
-        const int rc = run_tiled(o, cfg, cam, noisy, normals, positions, albedos, out);
+        const int rc = run_tiled(o, cfg, cam, noisy, normals, positions, albedos, out, out8);
         if (rc != 0) return rc;
         bool err = false;
         if (o.save) {
@@ -613,7 +640,8 @@ int run(const Options& o) {
             for (int f = 0; f < F; ++f) {
                 const std::string name = frame_file(o.output, f, o.exr ? ".exr" : ".png");
                 const int r = o.exr ? bmfr_exr_write_rgb(name.c_str(), W, H, out[f].data(), (size_t)W * 3, BMFR_EXR_ZIP)
-                                    : bmfr_png_write_rgb(name.c_str(), W, H, out[f].data(), (size_t)W * 3);
+                          : o.device_quantize ? bmfr_png_write_rgb8(name.c_str(), W, H, out8[f].data(), (size_t)W * 3)
+                                              : bmfr_png_write_rgb(name.c_str(), W, H, out[f].data(), (size_t)W * 3);
                 if (r != 0) err = true;
             }
         }
@@ -660,6 +688,13 @@ int run(const Options& o) {
         return hipEventRecord(uploaded[f], s);
     };
 
+    uint8_t* d_quantized = nullptr;  // --device-quantize: the frame's 8-bit RGB surface (reused in stream order)
+    if (o.device_quantize) {
+        HIP_CHECK(hipMalloc(&d_quantized, plane));
+        if (o.pipelined)
+            for (auto& v : out8)
+                if (hipHostRegister(v.data(), plane, hipHostRegisterDefault) == hipSuccess) registered.push_back(v.data());
+    }
     float* d_prev_pixel = nullptr;
     if (!pp_in.empty()) HIP_CHECK(hipMalloc(&d_prev_pixel, px_count * 2 * sizeof(float)));
     BMFR_CHECK(bmfr_set_profiling(ctx, 1, F));
@@ -687,8 +722,16 @@ int run(const Options& o) {
                                      hipMemcpyDeviceToHost, compute));
         }
         // Not timed upstream either: the result goes to the frame buffer (bmfr.cpp:478-480).
-        HIP_CHECK(hipMemcpyAsync(out[f].data(), bmfr_output(ctx), plane * sizeof(float), hipMemcpyDeviceToHost,
-                                 compute));
+        if (o.device_quantize) {  // 3 bytes per pixel instead of 12
+            bmfr_surface s;
+            bmfr_surface_default(&s);
+            s.data = d_quantized, s.format = BMFR_FORMAT_UNORM8X3, s.pitch = (size_t)W * 3, s.width = W, s.height = H;
+            BMFR_CHECK(bmfr_resolve_output(ctx, compute, BMFR_RESOLVE_OUTPUT, nullptr, &s));
+            HIP_CHECK(hipMemcpyAsync(out8[f].data(), d_quantized, plane, hipMemcpyDeviceToHost, compute));
+        } else {
+            HIP_CHECK(hipMemcpyAsync(out[f].data(), bmfr_output(ctx), plane * sizeof(float), hipMemcpyDeviceToHost,
+                                     compute));
+        }
     }
     HIP_CHECK(hipStreamSynchronize(compute));
     const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -755,7 +798,8 @@ int run(const Options& o) {
         for (int f = 0; f < F; ++f) {
             const std::string name = frame_file(o.output, f, o.exr ? ".exr" : ".png");
             const int r = o.exr ? bmfr_exr_write_rgb(name.c_str(), W, H, out[f].data(), (size_t)W * 3, BMFR_EXR_ZIP)
-                                : bmfr_png_write_rgb(name.c_str(), W, H, out[f].data(), (size_t)W * 3);
+                      : o.device_quantize ? bmfr_png_write_rgb8(name.c_str(), W, H, out8[f].data(), (size_t)W * 3)
+                                          : bmfr_png_write_rgb(name.c_str(), W, H, out[f].data(), (size_t)W * 3);
             if (r != 0) {
 #pragma omp critical
                 std::printf("Can't create image file on disk to location %s\n", name.c_str());
@@ -767,6 +811,7 @@ int run(const Options& o) {
 
     for (void* p : registered) (void)hipHostUnregister(p);
     (void)hipFree(d_prev_pixel);
+    (void)hipFree(d_quantized);
     for (auto& s : dev)
         for (auto& p : s) (void)hipFree(p);
     for (int f = 0; f < F; ++f) {

@@ -1337,18 +1337,10 @@ int bmfr_exr_write_rgb(const char* path, int width, int height, const float* rgb
     return 0;
 }
 
-int bmfr_png_write_rgb(const char* path, int width, int height, const float* rgb, size_t stride) {
-    if (width <= 0 || height <= 0 || !rgb || stride < (size_t)width * 3) return fail("bmfr_png_write_rgb: bad arguments");
-    std::vector<uint8_t> rows((size_t)height * (1 + (size_t)width * 3));
-    for (int y = 0; y < height; ++y) {
-        uint8_t* r = rows.data() + (size_t)y * (1 + (size_t)width * 3);
-        r[0] = 0;  // filter: none
-        for (int i = 0; i < width * 3; ++i) {
-            const float v = rgb[(size_t)y * stride + i];
-            const float c = v > 0.f ? (v < 1.f ? v : 1.f) : 0.f;  // NaN -> 0
-            r[1 + i] = (uint8_t)std::floor(c * 255.f + 0.5f);
-        }
-    }
+namespace {
+
+// An 8-bit RGB PNG from filter-prefixed rows (1 + width * 3 bytes each).
+int png_write_rows(const char* path, int width, int height, const std::vector<uint8_t>& rows) {
     std::vector<uint8_t> out = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
     std::vector<uint8_t> ihdr;
     put_be32(ihdr, (uint32_t)width);
@@ -1363,6 +1355,34 @@ int bmfr_png_write_rgb(const char* path, int width, int height, const float* rgb
     png_chunk(out, "IEND", {});
     if (!write_file(path, out)) return fail(std::string("cannot write ") + path);
     return 0;
+}
+
+}  // namespace
+
+int bmfr_png_write_rgb(const char* path, int width, int height, const float* rgb, size_t stride) {
+    if (width <= 0 || height <= 0 || !rgb || stride < (size_t)width * 3) return fail("bmfr_png_write_rgb: bad arguments");
+    std::vector<uint8_t> rows((size_t)height * (1 + (size_t)width * 3));
+    for (int y = 0; y < height; ++y) {
+        uint8_t* r = rows.data() + (size_t)y * (1 + (size_t)width * 3);
+        r[0] = 0;  // filter: none
+        for (int i = 0; i < width * 3; ++i) {
+            const float v = rgb[(size_t)y * stride + i];
+            const float c = v > 0.f ? (v < 1.f ? v : 1.f) : 0.f;  // NaN -> 0
+            r[1 + i] = (uint8_t)std::floor(c * 255.f + 0.5f);
+        }
+    }
+    return png_write_rows(path, width, height, rows);
+}
+
+int bmfr_png_write_rgb8(const char* path, int width, int height, const uint8_t* rgb, size_t pitch) {
+    if (width <= 0 || height <= 0 || !rgb || pitch < (size_t)width * 3) return fail("bmfr_png_write_rgb8: bad arguments");
+    std::vector<uint8_t> rows((size_t)height * (1 + (size_t)width * 3));
+    for (int y = 0; y < height; ++y) {
+        uint8_t* r = rows.data() + (size_t)y * (1 + (size_t)width * 3);
+        r[0] = 0;  // filter: none
+        std::memcpy(r + 1, rgb + (size_t)y * pitch, (size_t)width * 3);
+    }
+    return png_write_rows(path, width, height, rows);
 }
 
 }  // extern "C"

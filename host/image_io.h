@@ -16,6 +16,7 @@
 #define BMFR_IMAGE_IO_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -53,6 +54,11 @@ int bmfr_exr_write_rgb(const char *path, int width, int height, const float *rgb
 /* Write interleaved float RGB as an 8-bit RGB PNG: each sample clamped to
  * [0, 1] and quantised to round(255 v) (OpenImageIO's FLOAT -> UINT8). */
 int bmfr_png_write_rgb(const char *path, int width, int height, const float *rgb, size_t stride);
+
+/* Write packed 8-bit RGB rows (`pitch` bytes apart; BMFR_FORMAT_UNORM8X3, what
+ * bmfr_resolve_output quantises on the device by the same rule) as the same
+ * PNG: byte-identical to bmfr_png_write_rgb of the float image. */
+int bmfr_png_write_rgb8(const char *path, int width, int height, const uint8_t *rgb, size_t pitch);
 
 /* Last error message of this thread. */
 const char *bmfr_io_error(void);

@@ -493,7 +493,10 @@ typedef enum bmfr_format {       /* element formats of G-buffer planes */
     BMFR_FORMAT_UNORM8X4,        /* 4 B/px, v / 255, 4th ignored; albedo only */
     BMFR_FORMAT_OCT_SNORM16X2,   /* 4 B/px octahedral unit vector; normals only */
     BMFR_FORMAT_F32X2,           /* 8 B/px; motion only */
-    BMFR_FORMAT_F16X2            /* 4 B/px; motion only */
+    BMFR_FORMAT_F16X2,           /* 4 B/px; motion only */
+    /* output surfaces only (bmfr_resolve_output; bmfr_prepare_frame: unsupported) */
+    BMFR_FORMAT_UNORM8X3,        /* 3 B/px packed RGB (the PNG row format) */
+    BMFR_FORMAT_UNORM10X3A2      /* 4 B/px, one little-endian u32: R bits 0-9, G 10-19, B 20-29, A 30-31 */
 } bmfr_format;
 
 typedef struct bmfr_gbuffer {    /* what the renderer has; every pointer nullable */
@@ -660,6 +663,77 @@ typedef struct bmfr_state_view {
     float *result;
 } bmfr_state_view;
 bmfr_status bmfr_state(const bmfr_ctx *ctx, int previous, bmfr_state_view *out);
+
+/* ---- Output back end: from the context's state to a renderer's surface ----
+ * (no reference counterpart: the reference reads the float3 result back and
+ * quantises on the CPU, bmfr.cpp:479-480, 519-553).
+ *
+ * bmfr_resolve_output is the symmetric call to bmfr_prepare_frame: it writes
+ * the last processed frame into a surface in the format a swapchain or a post
+ * chain takes -- 8-bit, 10-bit or half / float, with a row pitch, an origin,
+ * rows bottom-up if wanted -- in one streaming kernel launch on `stream`.
+ *
+ * Which pixels.  The context's TILE (tile_*; the whole frame when untiled)
+ * is written, never the halo.  Frame pixel (x, y) goes to surface pixel
+ *     (origin_x + x,  origin_y + (flip_y ? H - 1 - y : y)),   H = image_height.
+ * Nothing else of the surface is written: not pixels outside the tile's image,
+ * not the bytes of a row past width * bytes_per_pixel (pitch padding), not a
+ * fourth byte after a UNORM8X3 pixel.  A negative origin lets a rank resolve
+ * into a tile-sized surface (origin = -tile_x, -tile_y); origin 0 lets all
+ * tiles of a grid resolve into one whole-frame surface.
+ *
+ * Source value v per channel.  Every line is one f32 operation rounded once,
+ * associated as written, never contracted.
+ *   BMFR_RESOLVE_OUTPUT: the last processed frame's TAA result, the plane
+ *      bmfr_output() names (display-referred, in [0, 1]).  albedo is ignored.
+ *   BMFR_RESOLVE_HDR:  v = a * f,  the linear colour the tone map starts from
+ *      (bmfr.cl:851-856): f = that frame's filtered_accumulated
+ *      (bmfr_state_view), a = `albedo`, the frame's albedo plane as given to
+ *      bmfr_process_frame -- the region with row stride region_width, f32x3,
+ *      or half3 widened exactly in an input_half context.
+ *
+ * Encoding.
+ *   F32X3        the bits of v.
+ *   F16X4        (half)v, round to nearest even; overflow goes to +-inf, NaN
+ *                stays NaN.  4th component: (half)alpha.
+ *   UNORM8X4 / UNORM8X3
+ *                c = v > 0 ? (v < 1 ? v : 1) : 0          (NaN -> 0)
+ *                q = (uint)floorf(c * 255.0f + 0.5f)
+ *                4th byte of X4: the same rule applied to alpha.
+ *   UNORM10X3A2  the same with 1023.0f; A = floorf(clamp(alpha) * 3.0f + 0.5f).
+ *   bgr swaps which source channel lands in component 0 and component 2, in
+ *   every format.
+ *
+ * Ordering.  The call reads the state of the last processed frame; it is
+ * enqueued on `stream` and must be ordered after that frame by the caller
+ * (the same stream, or an event).  Valid until the next bmfr_process_frame*,
+ * like bmfr_output().  It launches one kernel and changes neither the
+ * context's state, nor the frame status, nor what bmfr_frame_status waits for.
+ *
+ * Errors.  dst is checked first and without a context.
+ * BMFR_ERROR_INVALID_ARGUMENT: NULL dst or data; width or height <= 0; pitch <
+ * width * bytes_per_pixel; data or pitch not a multiple of the element's
+ * natural alignment (4 for F32X3, UNORM8X4 and UNORM10X3A2, 8 for F16X4, 1 for
+ * UNORM8X3); source not one of the two values; BMFR_RESOLVE_HDR with NULL
+ * albedo; then, with a context: NULL ctx, no processed frame yet, a pending
+ * _interior without its _border, or the mapped tile rectangle not inside
+ * [0, width) x [0, height).  BMFR_ERROR_UNSUPPORTED: a format outside the
+ * five listed.  Nothing is written when an error is returned. */
+typedef struct bmfr_surface {
+    void  *data;        /* device memory (or page-locked host memory the device can write) */
+    int    format;      /* F32X3 | F16X4 | UNORM8X4 | UNORM8X3 | UNORM10X3A2 */
+    size_t pitch;       /* bytes between surface rows */
+    int    width, height;      /* surface size in pixels */
+    int    origin_x, origin_y; /* surface pixel of frame pixel (0, 0); may be negative */
+    int    flip_y;      /* 1: frame row y lands on surface row origin_y + (H - 1 - y) */
+    int    bgr;         /* 1: channels 0 and 2 swapped (BGRA8, B10G10R10A2, ...) */
+    float  alpha;       /* 4th component of X4 / A2 formats */
+} bmfr_surface;
+typedef enum bmfr_resolve_source { BMFR_RESOLVE_OUTPUT = 0, BMFR_RESOLVE_HDR = 1 } bmfr_resolve_source;
+
+void bmfr_surface_default(bmfr_surface *s);   /* zeroes *s; alpha = 1 */
+bmfr_status bmfr_resolve_output(bmfr_ctx *ctx, void *stream, int source,
+                                const void *albedo, const bmfr_surface *dst);
 
 /* ---- Profiling: the CL_QUEUE_PROFILING_ENABLE + GPUTimer analogue ----
  * (bmfr.cpp:191, 386-412, 488-517).  When enabled, bmfr_process_frame records
