@@ -124,6 +124,11 @@ class Surface(C.Structure):
     ]
 
 
+class FireflyParams(C.Structure):
+    """bmfr_firefly_params: the rule of bmfr_suppress_fireflies (include/bmfr.h)."""
+    _fields_ = [("threshold", C.c_float), ("radius", C.c_int), ("floor", C.c_float), ("replace_nonfinite", C.c_int)]
+
+
 class StateView(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("noisy_accumulated", "spp", "filtered_accumulated", "tone_mapped",
@@ -158,6 +163,8 @@ SIGNATURES = {
     "bmfr_prepare_frame": (_I, [_P, _P, C.POINTER(GBuffer), C.POINTER(Prepared), _F2]),
     "bmfr_surface_default": (None, [C.POINTER(Surface)]),
     "bmfr_resolve_output": (_I, [_P, _P, _I, _P, C.POINTER(Surface)]),
+    "bmfr_firefly_default": (None, [C.POINTER(FireflyParams)]),
+    "bmfr_suppress_fireflies": (_I, [_P, _P, _P, _P, C.POINTER(FireflyParams), _P]),
     "bmfr_halo_copy": (_I, [_P, _P, C.POINTER(C.c_int), _I, _P, _I, C.POINTER(C.c_size_t)]),
     "bmfr_halo_need": (_I, [C.POINTER(Config), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bmfr_process_sequence": (_I, [_P, _P, _I, C.POINTER(FrameInputs), _F16, _F2, _I, C.POINTER(_P)]),
@@ -189,6 +196,7 @@ SIGNATURES = {
     "bmfr_debug_stamps": (_I, [_P, _P, C.c_size_t]),  # include/bmfr_debug.h
     "bmfr_debug_sync": (_I, [_P, _I, _I]),  # include/bmfr_debug.h
     "bmfr_debug_frame_launches": (_I, [_P, _I]),
+    "bmfr_debug_suppress_fireflies": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(FireflyParams), _P]),
     "bmfr_synth_frame_host": (_I, [_I, _I, _I, C.c_uint32, _P, _P, _P, _P, _P]),
     "bmfr_synth_frame_device": (_I, [_I, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "bmfr_synth_region_device": (_I, [_I, _I, _I, _I, _I, _I, _I, C.c_uint32, _P, _P, _P, _P, _P, _P]),

@@ -6,6 +6,7 @@
 // the Double_buffer swap (bmfr.cpp:122-135, 482-484).  No allocation happens
 // on the per-frame path; every call returns a status code.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +14,7 @@
 
 #include "../../include/bmfr.h"
 #include "../../include/bmfr_debug.h"
+#include "bmfr_firefly.h"
 #include "bmfr_launch.h"
 #include "bmfr_prepare.h"
 #include "bmfr_resolve.h"
@@ -1129,6 +1131,58 @@ bmfr_status bmfr_resolve_output(bmfr_ctx* c, void* stream, int source, const voi
     a.dy_step = d->flip_y ? -1 : 1;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_resolve(a, as_stream(stream)));
+}
+
+// ------------------------------------------------- firefly pre-filter ----
+void bmfr_firefly_default(bmfr_firefly_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof *p);
+    p->threshold = 2.0f;
+    p->radius = 1;
+    p->replace_nonfinite = 1;
+}
+
+namespace {
+
+// The filter over a width x height plane on the current device.
+bmfr_status suppress_fireflies(void* stream, const void* noisy, void* out, int width, int height, bool half,
+                               const bmfr_firefly_params* p, uint32_t* stats) {
+    if (!noisy || !out || !p || out == noisy) return BMFR_ERROR_INVALID_ARGUMENT;
+    const uintptr_t elem = half ? 2 : 4;
+    if (reinterpret_cast<uintptr_t>(noisy) % elem != 0 || reinterpret_cast<uintptr_t>(out) % elem != 0 ||
+        reinterpret_cast<uintptr_t>(stats) % sizeof(uint32_t) != 0)
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    if (!std::isfinite(p->threshold) || !(p->threshold > 0.0f) || (p->radius != 1 && p->radius != 2) ||
+        !std::isfinite(p->floor) || p->floor < 0.0f)
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    bmfr::FireflyArgs a{};
+    a.noisy = noisy;
+    a.out = out;
+    a.stats = stats;
+    a.threshold = p->threshold;
+    a.floor = p->floor;
+    a.replace_nonfinite = p->replace_nonfinite != 0;
+    a.rw = width;
+    a.rh = height;
+    return hip_status(bmfr::launch_firefly(a, half, p->radius, as_stream(stream)));
+}
+
+}  // namespace
+
+bmfr_status bmfr_suppress_fireflies(bmfr_ctx* c, void* stream, const void* noisy, void* out,
+                                    const bmfr_firefly_params* p, uint32_t* stats) {
+    if (!c) return BMFR_ERROR_INVALID_ARGUMENT;
+    DeviceGuard guard(c->device);
+    return suppress_fireflies(stream, noisy, out, c->sizes.region_width, c->sizes.region_height,
+                              c->cfg.input_half != 0, p, stats);
+}
+
+bmfr_status bmfr_debug_suppress_fireflies(void* stream, const void* noisy, void* out, int width, int height,
+                                          int half, const bmfr_firefly_params* p, uint32_t* stats) {
+    // planes are addressed at 32-bit byte offsets, as a context's (validate)
+    if (width <= 0 || height <= 0 || (unsigned long long)width * height * 12ull > 0xffffffffull)
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    return suppress_fireflies(stream, noisy, out, width, height, half != 0, p, stats);
 }
 
 bmfr_status bmfr_halo_copy(bmfr_ctx* c, void* stream, const int* rects, int n, void* buffer, int unpack,

@@ -462,14 +462,54 @@ class Denoiser(_Context):
             setattr(pr, name, t.data_ptr())
         return gb, pr, out
 
-    def process_gbuffer(self, g: dict, prev_vp, jitter, frame: int, stream=None) -> None:
+    # ---- Firefly pre-filter (include/bmfr.h bmfr_suppress_fireflies) ----
+    def firefly_args(self, noisy, out=None, threshold=2.0, radius=1, floor=0.0, replace_nonfinite=True, stats=None):
+        """The checked arguments of bmfr_suppress_fireflies -> (out,
+        bmfr_firefly_params); a caller that repeats a call keeps them.  Runs
+        before the call, which would read or write a wrong plane out of bounds."""
+        dtypes = {torch.float16 if self.cfg.input_half else torch.float32: (None, 3)}
+        self._check_plane("noisy", noisy, dtypes)
+        if out is None:
+            out = torch.empty_like(noisy)
+        self._check_plane("out", out, dtypes)
+        if stats is not None:
+            if not isinstance(stats, torch.Tensor) or stats.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
+                    or stats.numel() != 2 or not stats.is_contiguous() or stats.device.type != "cuda" \
+                    or (stats.device.index or 0) != self.device:
+                raise ValueError(f"stats must be a contiguous tensor of two 32-bit integers on cuda:{self.device}")
+        p = _lib.FireflyParams()
+        self.lib.bmfr_firefly_default(C.byref(p))
+        p.threshold, p.radius, p.floor = float(threshold), int(radius), float(floor)
+        p.replace_nonfinite = int(bool(replace_nonfinite))
+        return out, p
+
+    def suppress_fireflies(self, noisy, out=None, threshold=2.0, radius=1, floor=0.0, replace_nonfinite=True,
+                           stats=None, stream=None):
+        """bmfr_suppress_fireflies: the noisy plane (the region; float3, or
+        half3 with input_half) with every pixel held to `threshold` times its
+        brightest neighbour within `radius` (1 or 2), never below the luminance
+        `floor`, and pixels with a NaN / inf channel zeroed
+        (replace_nonfinite), into `out` (default: a new plane; never `noisy`
+        itself) in one kernel launch.  stats: an int32 tensor of two counters,
+        {clamped, replaced}, which the call adds to.  -> out."""
+        out, p = self.firefly_args(noisy, out, threshold, radius, floor, replace_nonfinite, stats)
+        check(self.lib.bmfr_suppress_fireflies(self.handle, _stream(stream), _ptr(noisy), _ptr(out), C.byref(p),
+                                               _ptr(stats)), "bmfr_suppress_fireflies")
+        return out
+
+    def process_gbuffer(self, g: dict, prev_vp, jitter, frame: int, stream=None, firefly=None) -> None:
         """prepare(g), then process_frame on the prepared planes.  The
         denoiser owns two sets of prepared planes and alternates them: K1 of
         frame f + 1 reads frame f's normals and positions, which must stay
         unmodified until then.  From frame 1 on: with object_transforms or
         prev_object_id in g, last frame's planes moved by them are the
         previous planes, else last frame's planes as they are; with motion in
-        g, the prepared prev_pixel replaces the projection through prev_vp."""
+        g, the prepared prev_pixel replaces the projection through prev_vp.
+        firefly: a dict of suppress_fireflies' parameters (threshold, radius,
+        floor, replace_nonfinite, stats; {} = the defaults): the prepared
+        noisy plane goes through the filter, into a third plane the denoiser
+        owns, before process_frame reads it.  None: no filter, the launches
+        of a call without it."""
         n = self.sizes.region_width * self.sizes.region_height
         if getattr(self, "_prepared_sets", None) is None:
             dev = torch.device("cuda", self.device)
@@ -491,7 +531,12 @@ class Denoiser(_Context):
                 want.append("prev_pixel")
                 prev_pixel = cur["prev_pixel"]
         self.prepare(g, jitter, out={k: cur[k] for k in want}, stream=stream)
-        self.process_frame(cur["noisy"], cur["normals"], cur["positions"], cur["albedo"], prev_vp, jitter, frame,
+        noisy = cur["noisy"]
+        if firefly is not None:
+            if getattr(self, "_filtered_noisy", None) is None:
+                self._filtered_noisy = torch.empty_like(noisy)
+            noisy = self.suppress_fireflies(noisy, out=self._filtered_noisy, stream=stream, **firefly)
+        self.process_frame(noisy, cur["normals"], cur["positions"], cur["albedo"], prev_vp, jitter, frame,
                            prev_normals=prev_normals if frame > 0 else None,
                            prev_positions=prev_positions if frame > 0 else None, stream=stream,
                            prev_pixel=prev_pixel, aux=g.get("aux"))

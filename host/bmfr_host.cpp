@@ -81,6 +81,11 @@ struct Options {
     // device surface (bmfr_resolve_output, BMFR_FORMAT_UNORM8X3); the host reads
     // back 3 bytes per pixel instead of 12 and writes them as they are
     bool device_quantize = false;
+    // --firefly K [--firefly-radius R]: each frame's noisy plane goes through
+    // bmfr_suppress_fireflies (threshold K, radius R) on the device before
+    // bmfr_process_frame reads it; 0 = off
+    float firefly = 0.f;
+    int firefly_radius = 1;
 };
 
 void usage() {
@@ -111,7 +116,11 @@ void usage() {
         "  --prev-pixel PREFIX    read such files and pass them as bmfr_frame_inputs.prev_pixel from\n"
         "                         frame 1 on, instead of projecting with the camera matrices\n"
         "  --device-quantize      PNG output only: quantise on the GPU (bmfr_resolve_output into an 8-bit RGB\n"
-        "                         surface) and read back 3 bytes per pixel instead of 12; the same files\n");
+        "                         surface) and read back 3 bytes per pixel instead of 12; the same files\n"
+        "  --firefly K            filter each frame's noisy plane on the GPU before the frame (bmfr_suppress_fireflies:\n"
+        "                         a pixel at most K x its brightest neighbour, NaN / inf pixels zeroed); K = 2 is the\n"
+        "                         library's default\n"
+        "  --firefly-radius R     the filter's window radius, 1 (default) or 2\n");
 }
 
 bool parse_args(int argc, char** argv, Options& o) {
@@ -153,6 +162,8 @@ bool parse_args(int argc, char** argv, Options& o) {
         else if (a == "--dump-prev-pixel") o.dump_prev_pixel = next("a prefix");
         else if (a == "--prev-pixel") o.prev_pixel = next("a prefix");
         else if (a == "--device-quantize") o.device_quantize = true;
+        else if (a == "--firefly") o.firefly = (float)std::atof(next("a threshold"));
+        else if (a == "--firefly-radius") o.firefly_radius = std::atoi(next("1 or 2"));
         else if (a == "-h" || a == "--help") {
             usage();
             std::exit(0);
@@ -366,7 +377,11 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
         float* in[2][4] = {};  // current / previous region planes: noisy, normal, position, albedo
         bmfr_exchange* x = nullptr;
         uint8_t* quantized = nullptr;  // --device-quantize: the tile's 8-bit RGB surface
+        float* filtered = nullptr;     // --firefly: the region's filtered noisy plane
     };
+    bmfr_firefly_params firefly;
+    bmfr_firefly_default(&firefly);
+    firefly.threshold = o.firefly, firefly.radius = o.firefly_radius;
     std::vector<Tile> t(T);
     std::vector<bmfr_comm*> comms(T, nullptr);
     if (o.gpus == T && T > 1) {
@@ -390,6 +405,7 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
             for (auto& p : s) HIP_CHECK(hipMalloc(&p, q.sz.region_bytes));
         BMFR_CHECK(bmfr_exchange_create(q.ctx, &q.cfg, tiles.data(), T, r, comms[r], &q.x));
         if (o.device_quantize) HIP_CHECK(hipMalloc(&q.quantized, (size_t)q.cfg.tile_width * q.cfg.tile_height * 3));
+        if (o.firefly != 0.f) HIP_CHECK(hipMalloc(&q.filtered, q.sz.region_bytes));
     }
     std::printf("Processing %d frames (%dx%d) as %dx%d tiles, halo %d px, on %d GPU(s).\n", F, W, H, o.tiles_x,
                 o.tiles_y, o.tile_halo, o.gpus);
@@ -414,6 +430,10 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
                                            q.stream));
             float** pv = q.in[(f + 1) & 1];
             in[r] = {d[0], d[1], d[2], d[3], f > 0 ? pv[1] : nullptr, f > 0 ? pv[2] : nullptr};
+            if (q.filtered) {  // stream order: the previous frame has read the plane
+                BMFR_CHECK(bmfr_suppress_fireflies(q.ctx, q.stream, d[0], q.filtered, &firefly, nullptr));
+                in[r].noisy = q.filtered;
+            }
         }
         if (f == 0) {
             for (int r = 0; r < T; ++r)
@@ -489,6 +509,7 @@ int run_tiled(const Options& o, const bmfr_config& base, const Camera& cam, cons
         HIP_CHECK(hipSetDevice(q.device));
         bmfr_exchange_destroy(q.x);
         (void)hipFree(q.quantized);
+        (void)hipFree(q.filtered);
         for (auto& s : q.in)
             for (auto& p : s) (void)hipFree(p);
         (void)hipStreamDestroy(q.stream);
@@ -695,6 +716,11 @@ int run(const Options& o) {
             for (auto& v : out8)
                 if (hipHostRegister(v.data(), plane, hipHostRegisterDefault) == hipSuccess) registered.push_back(v.data());
     }
+    float* d_filtered = nullptr;  // --firefly: the frame's filtered noisy plane (reused in stream order)
+    bmfr_firefly_params firefly;
+    bmfr_firefly_default(&firefly);
+    firefly.threshold = o.firefly, firefly.radius = o.firefly_radius;
+    if (o.firefly != 0.f) HIP_CHECK(hipMalloc(&d_filtered, plane * sizeof(float)));
     float* d_prev_pixel = nullptr;
     if (!pp_in.empty()) HIP_CHECK(hipMalloc(&d_prev_pixel, px_count * 2 * sizeof(float)));
     BMFR_CHECK(bmfr_set_profiling(ctx, 1, F));
@@ -711,6 +737,10 @@ int run(const Options& o) {
             HIP_CHECK(hipMemcpyAsync(d_prev_pixel, pp_in[f].data(), px_count * 2 * sizeof(float), hipMemcpyHostToDevice,
                                      compute));
             in.prev_pixel = d_prev_pixel;
+        }
+        if (d_filtered) {
+            BMFR_CHECK(bmfr_suppress_fireflies(ctx, compute, d[0], d_filtered, &firefly, nullptr));
+            in.noisy = d_filtered;
         }
         const int matrix_index = f == 0 ? 0 : f - 1;  // bmfr.cpp:440
         BMFR_CHECK(bmfr_process_frame(ctx, compute, &in, &cam.matrices[16 * matrix_index], &cam.offsets[2 * f], f));
@@ -811,6 +841,7 @@ int run(const Options& o) {
 
     for (void* p : registered) (void)hipHostUnregister(p);
     (void)hipFree(d_prev_pixel);
+    (void)hipFree(d_filtered);
     (void)hipFree(d_quantized);
     for (auto& s : dev)
         for (auto& p : s) (void)hipFree(p);

@@ -735,6 +735,85 @@ void bmfr_surface_default(bmfr_surface *s);   /* zeroes *s; alpha = 1 */
 bmfr_status bmfr_resolve_output(bmfr_ctx *ctx, void *stream, int source,
                                 const void *albedo, const bmfr_surface *dst);
 
+/* ---- Firefly pre-filter: an outlier clamp ahead of the block fit ----
+ * (no reference counterpart: the reference's dataset is clean.  A renderer's
+ * 1-spp buffers are not: one firefly is a huge residual in a 32x32 block's
+ * least-squares fit and bends the whole block's fitted colour, the temporal
+ * accumulation keeps it for about 1 / blend_alpha frames, and a NaN or inf
+ * sample poisons the block and then its history -- only the feature columns
+ * of the design matrix are NaN-guarded, bmfr.cl:448-473, not the colour.)
+ *
+ * bmfr_suppress_fireflies filters the `noisy` plane into `out`: a pixel may be
+ * at most `threshold` times as bright as its brightest neighbour.  One kernel
+ * launch on `stream`, between bmfr_prepare_frame (or the renderer) and
+ * bmfr_process_frame, which then takes `out` as bmfr_frame_inputs.noisy.
+ *
+ * Planes.  noisy and out cover the context's region (bmfr_sizes.region_*),
+ * row stride region_width, in the context's input format: float3, or half3
+ * with input_half -- the plane bmfr_process_frame reads as
+ * bmfr_frame_inputs.noisy and bmfr_prepare_frame writes as
+ * bmfr_prepared.noisy.  Device memory aligned to the element (planes aligned
+ * to 16 bytes take the kernel's wide accesses).
+ *
+ * Arithmetic: every line is one f32 operation rounded once, associated as
+ * written, never contracted; division correctly rounded; half values widen
+ * exactly; a half result is the f32 result rounded to nearest even.
+ *
+ *  Y(q) = (0.2126f * r + 0.7152f * g) + 0.0722f * b      the luminance of pixel q
+ *  For a pixel p:
+ *  1. If any channel of p is NaN or +-inf, p is invalid: with
+ *     replace_nonfinite, out = (+0, +0, +0) and stats[1] counts it; otherwise
+ *     p's bytes are copied.  Either way p is done.
+ *  2. m = the maximum of Y(q) over the pixels q != p with |dx|, |dy| <= radius
+ *     that lie inside the region and have a finite Y(q).  No such q: p's bytes
+ *     are copied.
+ *  3. limit = threshold * m;   if (!(limit > floor)) limit = floor
+ *  4. If Y(p) > limit:  s = limit / Y(p);  out_c = c * s per channel c, and
+ *     stats[0] counts it.  Otherwise p's bytes are copied unchanged, the sign
+ *     of a zero and denormals included.
+ *
+ * Limits of the rule, on purpose.  Two adjacent fireflies protect each other
+ * (each is the other's brightest neighbour).  With floor = 0 a lone lit pixel
+ * among exactly black neighbours is scaled to 0 (m = 0): content with truly
+ * black regions -- an unlit background, a mask -- wants a floor near the
+ * smallest luminance it considers signal.  threshold 2 at radius 1 is the
+ * default: on the test scenes it touches 0.4 % of the pixels and cuts the
+ * damage x50 fireflies do to the output about fourfold; threshold 1 clamps
+ * every ninth pixel and is worse than no filter (tests/test_firefly_cpu.py).
+ *
+ * stats (nullable): two uint32_t in device memory, {clamped, replaced}.  The
+ * call adds to them; the caller zeroes them.
+ *
+ * Launch and state.  The call reads no state and changes none: not the state
+ * planes, not the frame status, not what bmfr_frame_status waits for.  It is
+ * legal before any frame has been processed.
+ *
+ * Tiled contexts.  The window is clipped to the region.  A pixel whose window
+ * lies inside the region, or is cut only by the image border, equals the
+ * untiled filter's pixel; only the outermost `radius` rings along a region
+ * edge inside the image differ.  K1 reads the current frame's colour over the
+ * blocks that cover the tile grown by one pixel (frame_params_cfg,
+ * bmfr_capi.hip: 32-pixel blocks, bmfr_kernels.h), so at most 32 pixels past
+ * the tile, mirrored into the image at its border; tile_halo >= 34 leaves the
+ * rings that differ, 33 and 34 pixels out at radius 2, just beyond that.  A
+ * tiled pipeline fed filtered region planes therefore still equals the
+ * untiled one bit for bit.
+ *
+ * Errors.  BMFR_ERROR_INVALID_ARGUMENT, before anything is enqueued and with
+ * nothing written: NULL ctx, noisy, out or p; out == noisy (a stencil cannot
+ * run in place; any other overlap is undefined); a plane not aligned to its
+ * element (4 bytes, 2 with input_half) or stats not aligned to 4; threshold
+ * not finite or not > 0; radius outside {1, 2}; floor negative or not finite. */
+typedef struct bmfr_firefly_params {
+    float threshold;          /* k > 0, finite: a pixel may be at most k x its brightest neighbour. Default 2 */
+    int   radius;             /* 1 or 2: the (2r+1)^2 window without its centre. Default 1 */
+    float floor;              /* >= 0, finite: the limit is never below this luminance. Default 0 */
+    int   replace_nonfinite;  /* 1 (default): a pixel with a NaN / +-inf channel becomes (0,0,0); 0: it passes through */
+} bmfr_firefly_params;
+void bmfr_firefly_default(bmfr_firefly_params *p);
+bmfr_status bmfr_suppress_fireflies(bmfr_ctx *ctx, void *stream, const void *noisy, void *out,
+                                    const bmfr_firefly_params *p, uint32_t *stats /* device, nullable */);
+
 /* ---- Profiling: the CL_QUEUE_PROFILING_ENABLE + GPUTimer analogue ----
  * (bmfr.cpp:191, 386-412, 488-517).  When enabled, bmfr_process_frame records
  * HIP events around its two kernels; bmfr_get_profile synchronises on them and

@@ -28,6 +28,12 @@ bmfr_status bmfr_debug_sync(bmfr_ctx *ctx, int max_polls, int k1_delay);
  * flags) at any size, 2: K1, then K2.  Results are the same bit for bit;
  * the tests use it to run the one-launch kernel at 4K. */
 bmfr_status bmfr_debug_frame_launches(bmfr_ctx *ctx, int launches);
+/* bmfr_debug_suppress_fireflies: bmfr_suppress_fireflies without a context, on
+ * a width x height plane (half3 if `half`, else float3) of the current device.
+ * The smallest region a context has is 32 x 32; the tests use this entry to
+ * run the kernel on planes narrower than its window and its pixel groups. */
+bmfr_status bmfr_debug_suppress_fireflies(void *stream, const void *noisy, void *out, int width, int height,
+                                          int half, const bmfr_firefly_params *p, uint32_t *stats);
 #ifdef __cplusplus
 }
 #endif
