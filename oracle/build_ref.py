@@ -25,16 +25,18 @@ import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from ref_configs import (FULL_REF_CONFIGS, KNOB_REF_CONFIGS, REF_CONFIGS, REF_MODES,  # noqa: E402
+from ref_configs import (FULL_REF_CONFIGS, GEOMETRY_REF_CONFIGS, KNOB_REF_CONFIGS, REF_CONFIGS, REF_MODES,  # noqa: E402
                          SHAPE_REF_CONFIGS)
 
 # (configurations, the modes they are compiled in).  The shape sweep is compared
-# bit for bit only, so it gets the strict build alone.
+# bit for bit only, so it gets the strict build alone; the geometry sweep's
+# fast_fit bar is measured against the distance between the two builds.
 BUILDS = (
     (REF_CONFIGS, ("strict", "default")),
     (FULL_REF_CONFIGS, ("strict", "default")),
     (KNOB_REF_CONFIGS, ("strict", "default")),
     (SHAPE_REF_CONFIGS, ("strict",)),
+    (GEOMETRY_REF_CONFIGS, ("strict", "default")),
 )
 
 CLANG = "/opt/rocm/lib/llvm/bin/clang"

@@ -273,6 +273,46 @@ SHAPE_REF_CONFIGS = {
 }
 
 
+# The geometry sweep (tests/test_geometry_cpu.py, tests/test_gpu_geometry.py):
+# frame sizes at the accepted end of the library's rule -- an axis n is valid
+# when n >= 32 and workset(n) + 30 <= 2 n, so 32 and everything from 47 up --
+# with odd widths and heights.  Named g<W>x<H>_<h|f><B>.  Content: scene "rand"
+# with seed GEOMETRY_SEED.  17 frames go through all 16 block offsets (both
+# -16s included), 6 frames still reach +-14 in y.  What each size is there for
+# is computed from the block-offset table in tests/test_geometry_cpu.py.
+GEOMETRY_SCENE = "rand"
+GEOMETRY_SEED = 7
+GEOMETRY_GENERIC_LISTS = {7: ((0,), (4, 5, 6)), 12: ((0, 3), (10, 11, 12, 7, 8, 9, 4))}
+
+
+def _geometry_config(w, h, half_tmp, buffers, frames) -> RefConfig:
+    lists = {13: (NOT_SCALED_DEFAULT, SCALED_DEFAULT), 16: (NOT_SCALED_DEFAULT, SCALED_THIRD_ORDER),
+             **GEOMETRY_GENERIC_LISTS}[buffers]
+    return RefConfig(f"g{w}x{h}_{'h' if half_tmp else 'f'}{buffers}", w, h, not_scaled=lists[0], scaled=lists[1],
+                     half_tmp=half_tmp, frames=frames, seed=GEOMETRY_SEED)
+
+
+GEOMETRY_REF_CONFIGS = {
+    c.name: c
+    for c in (
+        _geometry_config(32, 32, 1, 13, 17),    # smallest frame; -32 -> 31; 2 x 2 blocks; one TAA tile
+        _geometry_config(32, 32, 0, 13, 6),     # the same on the row-split K1
+        _geometry_config(47, 47, 1, 13, 17),    # 93 -> 0; odd stride
+        _geometry_config(47, 47, 1, 16, 6),     # B = 16 at the limit
+        _geometry_config(65, 47, 1, 13, 17),    # one-pixel block column; 1 px past a TAA tile in x
+        # one-pixel block row; 1 px past the 16-high TAA tile, 5 past the 12-high.  10 frames: the y offset -16, on which
+        # the last block row holds image row 64 alone, is frame 9's
+        _geometry_config(47, 65, 0, 16, 10),
+        _geometry_config(97, 79, 1, 13, 6),     # height 79: work-item 96 + 29 mirrors onto pixel 32
+        _geometry_config(97, 79, 1, 7, 6),      # generic-count K1 at an odd size
+        _geometry_config(129, 53, 1, 13, 17),   # 1 px past two TAA tiles; H mod 16 = 5, mod 12 = 5
+        _geometry_config(129, 53, 0, 13, 6),
+        _geometry_config(67, 131, 1, 16, 6),    # tall; H mod 16 = 3, mod 12 = 11
+        _geometry_config(67, 131, 1, 12, 6),    # generic K1, tall
+    )
+}
+
+
 # Build modes of the reference: "strict" fixes the arithmetic OpenCL leaves to
 # the implementation (no contraction, correctly rounded / and sqrt) and is the
 # one the oracle is pinned to bit-for-bit; "default" is what bmfr.cpp's

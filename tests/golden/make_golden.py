@@ -15,13 +15,17 @@ Other content and other configurations: make(name, out_dir, configs, scene,
 seed) takes the configuration dictionary and a scene of tests/scenes_np.py; the
 fixture then records the scene, the seed and the six knob texts of the
 configuration.  --knobs makes the fixtures of tests/test_knobs_cpu.py
-(ref_configs.KNOB_REF_CONFIGS on scene rand) under tests/golden/knobs/.
+(ref_configs.KNOB_REF_CONFIGS on scene rand) under tests/golden/knobs/,
+--geometry those of tests/test_geometry_cpu.py (GEOMETRY_REF_CONFIGS, the first
+geometry_util.GOLDEN_FRAMES frames of each) under tests/golden/geometry/.
 
 Usage (GPU box): python tests/golden/make_golden.py [--out DIR] [config ...]
                  python tests/golden/make_golden.py --knobs [--out DIR] [config ...]
+                 python tests/golden/make_golden.py --geometry [--out DIR] [config ...]
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import os
 import sys
@@ -35,9 +39,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import ref_run  # noqa: E402
+import geometry_util  # noqa: E402
 import knob_util  # noqa: E402
 import scenes_np  # noqa: E402
-from ref_configs import KNOB_REF_CONFIGS, REF_CONFIGS, fmt_g  # noqa: E402
+from ref_configs import (GEOMETRY_REF_CONFIGS, GEOMETRY_SCENE, GEOMETRY_SEED, KNOB_REF_CONFIGS, REF_CONFIGS,  # noqa: E402
+                         fmt_g)
 from seq_util import EXACT_KEYS, POWR_KEYS, digest, frame_inputs, input_digest, run_loop, sample_idx  # noqa: E402
 
 
@@ -91,8 +97,13 @@ if __name__ == "__main__":
     ap.add_argument("configs", nargs="*")
     ap.add_argument("--out", help="output directory (default: tests/golden, with --knobs tests/golden/knobs)")
     ap.add_argument("--knobs", action="store_true", help="the knob fixtures: KNOB_REF_CONFIGS on scene rand")
+    ap.add_argument("--geometry", action="store_true", help="the geometry fixtures: GEOMETRY_REF_CONFIGS on scene rand")
     a = ap.parse_args()
-    if a.knobs:
+    if a.geometry:
+        for n in a.configs or list(geometry_util.GOLDEN_FRAMES):
+            cut = {n: dataclasses.replace(GEOMETRY_REF_CONFIGS[n], frames=geometry_util.GOLDEN_FRAMES[n])}
+            print(make(n, a.out or os.path.join(HERE, "geometry"), cut, GEOMETRY_SCENE, GEOMETRY_SEED), flush=True)
+    elif a.knobs:
         for n in a.configs or KNOB_GOLDEN:
             assert knob_util.scene_of(n) == ("rand", False), n
             print(make(n, a.out or os.path.join(HERE, "knobs"), KNOB_REF_CONFIGS, "rand", knob_util.SEED), flush=True)

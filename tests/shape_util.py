@@ -62,7 +62,11 @@ def aux_case(name: str):
     position 1 replaced by caller-supplied planes; the plane index rotates
     with the shape.  -> (not_scaled, scaled, names): names[k] is the
     aux_np.PLANES key of the monomial plane k holds (None: not named)."""
-    rc = SHAPE_REF_CONFIGS[name]
+    return aux_case_of(SHAPE_REF_CONFIGS[name])
+
+
+def aux_case_of(rc):
+    """aux_case for any configuration with a generic (non-canonical) list."""
     ns = len(rc.not_scaled)
     codes = rc.not_scaled + rc.scaled
     k = (ns + len(rc.scaled)) % 4
