@@ -20,7 +20,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 
 import ref_run  # noqa: E402
 from ref_configs import FULL_REF_CONFIGS  # noqa: E402
-from test_gpu_reference_fullsize import CASES, DIGESTS, cameras, frame_planes, sha  # noqa: E402
+from fullsize_util import CASES, DIGESTS, cameras, frame_planes, sha  # noqa: E402
 
 
 def make(case: str, build: str, half_in: int) -> dict:

@@ -18,9 +18,9 @@ import numpy as np
 
 import scenes_np
 from ref_configs import KNOB_REF_CONFIGS, knob_set_of
+from seq_util import PLANES
 
 SEED = 2
-PLANES = ("noisy", "normals", "positions", "albedo")
 LIT_DELTA = np.float32(1 + 2.0 ** -20)
 LIT_DISTANCE_SQ = np.float32(LIT_DELTA * LIT_DELTA)  # 1.0000019
 

@@ -19,7 +19,19 @@ import scenes_np
 
 T = (0.25, -0.5, 0.125)   # the world's translation per frame
 QUANTUM = 2.0 ** -8
-PLANES = ("noisy", "normals", "positions", "albedo")
+# width, height and halo of the reach scenario: 40 px of motion against a 40 px halo on a 2 x 2 grid
+# (tests/test_gpu_reach.py by matrix, tests/test_gpu_motion_input.py through planes)
+REACH_SIZE = (320, 256, 40)
+
+
+def shifted(vp, dx: float, width: int):
+    """The column-major VP with clip x += (2 dx / width) w: every reprojection
+    lands dx pixels further right (bmfr.cl:343-355)."""
+    k = 2.0 * dx / width
+    m = list(vp)
+    for c in range(4):  # row 0 += k * row 3
+        m[4 * c] += k * m[4 * c + 3]
+    return m
 
 
 def scene_frame(scene: str, W: int, H: int, f: int) -> dict:

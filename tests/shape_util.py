@@ -10,7 +10,6 @@ import scenes_np
 from ref_configs import SHAPE_REF_CONFIGS, SHAPE_SCENE
 
 NAMES = list(SHAPE_REF_CONFIGS)
-PLANES = ("noisy", "normals", "positions", "albedo")
 NAME_OF = {code: nm for nm, code in aux_np.CODE_OF.items()}
 
 

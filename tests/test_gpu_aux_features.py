@@ -23,36 +23,17 @@ from __future__ import annotations
 
 import functools
 
-import numpy as np
 import pytest
-import torch
 
 import aux_np
-import bmfr_amd
 import pyoracle
-from ref_configs import REF_CONFIGS
+from parity_harness import device_frames, fused_frames
+from ref_configs import REF_CONFIGS, RefConfig
+from seq_util import FUSED_KEYS, compare_exact, compare_nan_aware
 
 pytestmark = pytest.mark.gpu
 
-KEYS = {"result": None, "noisy": "noisy_accumulated", "acc": "filtered_accumulated", "spp": "spp",
-        "prev_pixel": "prev_frame_pixel"}
-NAN_VP = [float("nan")] * 16
-GARBAGE_JITTER = [float("nan"), 1e30]
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()  # a copy: generated planes may be read-only
-
-
-def _state(den, n) -> dict:
-    f32 = lambda m: torch.empty(m, device="cuda")  # noqa: E731
-    out = {"result": den.copy_output(f32(3 * n))}
-    for k, name in KEYS.items():
-        if name is not None:
-            out[k] = den.copy_state(name, torch.empty(n, dtype=torch.uint8, device="cuda") if k == "spp"
-                                    else f32((2 if k == "prev_pixel" else 3) * n))
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().copy() for k, v in out.items()}
+KEYS = tuple(FUSED_KEYS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -62,85 +43,22 @@ def frames_of(source, W, H, frames):
     return tuple(src(f) for f in range(frames))
 
 
-def aux_of(names, fr, W, H):
-    """The frame's aux planes on the device (None where not supplied)."""
-    return [None if p is None else _dev(p)
-            for p in aux_np.aux_planes(names, fr["normals"], fr["positions"], fr["albedo"], W, H)]
-
-
-def denoise(W, H, not_scaled, scaled, half, source, frames, names=(), library_powr=0, mode="frame",
-            prev_pixel=None):
-    """The Denoiser over the content, frame by frame -> per-frame state.
-    names: the aux planes' contents (aux_np.PLANES keys).  mode: "frame",
-    "split" (_interior + _border) or "sequence" (one process_sequence call).
-    prev_pixel: per-frame planes (numpy) that replace the camera, which is
-    then NaN."""
-    den = bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(image_width=W, image_height=H, not_scaled=tuple(not_scaled),
-                                                scaled=tuple(scaled), use_half_precision_in_tmp_data=half,
-                                                library_powr=library_powr))
-    n = W * H
+def denoise(W, H, not_scaled, scaled, half, source, frames, names=(), library_powr=0, mode="frame", replay=None):
+    """The Denoiser over the content, frame by frame -> per-frame state
+    (parity_harness.fused_frames).  names: the aux planes' contents
+    (aux_np.PLANES keys).  mode: "frame", "split" (_interior + _border) or
+    "sequence" (one process_sequence call).  replay: the records of a run
+    whose prev_frame_pixel planes replace the camera, which is then NaN."""
+    rc = RefConfig(f"aux{W}x{H}", W, H, tuple(not_scaled), tuple(scaled), half)
     content = frames_of(source, W, H, frames)
-    if mode == "sequence":
-        fr_dev, cams, outs = [], [], []
-        for fr in content:
-            d = {k: _dev(fr[k]) for k in ("noisy", "normals", "positions", "albedo")}
-            d["aux"] = aux_of(names, fr, W, H)
-            fr_dev.append(d)
-            cams.append((fr["prev_vp"], fr["jitter"]))
-            outs.append(torch.empty(3 * n, device="cuda"))
-        den.process_sequence(fr_dev, cams, 0, outputs=outs)
-        torch.cuda.synchronize()
-        assert den.frame_status() == 0
-        return [{"result": o.cpu().numpy().copy()} for o in outs], _state(den, n)
-    out = []
-    for f, fr in enumerate(content):
-        d = {k: _dev(fr[k]) for k in ("noisy", "normals", "positions", "albedo")}
-        vp, jit, plane = fr["prev_vp"], fr["jitter"], None
-        if prev_pixel is not None:
-            vp, jit = NAN_VP, GARBAGE_JITTER
-            plane = _dev(prev_pixel[f]) if f > 0 else torch.full((2 * n,), float("nan"), device="cuda")
-        args = (d["noisy"], d["normals"], d["positions"], d["albedo"], vp, jit, f)
-        kw = dict(prev_pixel=plane, aux=aux_of(names, fr, W, H))
-        if mode == "split":
-            den.process_frame_interior(*args, **kw)
-            den.process_frame_border(*args, **kw)
-        else:
-            den.process_frame(*args, **kw)
-        out.append(_state(den, n))
-    assert den.frame_status() == 0
-    return out
+    return fused_frames(rc, device_frames(content.__getitem__, frames, W, H, aux_names=names),
+                        library_powr=library_powr, mode=mode, replay=replay)
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_named(W, H, not_scaled, scaled, half, source, frames):
     cfg = pyoracle.make_cfg(W, H, not_scaled, scaled, half)
     return aux_np.run(pyoracle.OracleLoop(cfg), source, frames)
-
-
-def compare_bytes(got, want, where, keys=KEYS):
-    for f, (g, w) in enumerate(zip(got, want)):
-        for k in keys:
-            if k not in g:
-                continue
-            a, b = np.frombuffer(g[k].tobytes(), np.uint8), np.frombuffer(w[k].tobytes(), np.uint8)
-            assert a.size == b.size, (where, f, k, a.size, b.size)
-            bad = np.flatnonzero(a != b)
-            assert bad.size == 0, f"{where} frame {f} {k}: {bad.size} of {a.size} bytes differ, first at byte {bad[0]}"
-
-
-def compare_nan_aware(got, want, where, keys=KEYS):
-    """The same NaN positions, and the same bits everywhere else."""
-    for f, (g, w) in enumerate(zip(got, want)):
-        for k in keys:
-            a, b = g[k].reshape(-1), w[k].reshape(-1)
-            assert a.shape == b.shape and a.dtype == b.dtype, (where, f, k)
-            if a.dtype != np.float32:
-                assert (a == b).all(), (where, f, k)
-                continue
-            na, nb = np.isnan(a), np.isnan(b)
-            assert (na == nb).all(), f"{where} frame {f} {k}: NaN at {int(na.sum())} vs {int(nb.sum())} places"
-            bad = np.flatnonzero((a.view(np.uint32) != b.view(np.uint32)) & ~na)
-            assert bad.size == 0, f"{where} frame {f} {k}: {bad.size} of {a.size} differ, first at {bad[:5]}"
 
 
 # ---------------------------------------------------------------- part A ----
@@ -190,10 +108,10 @@ def test_monomial_planes_equal_named_codes(case, library_powr, gpu):
     nans = c["source"].startswith("clamp")
     if library_powr == 0:
         want = oracle_named(*size, c["not_scaled"], c["scaled"], c["half"], c["source"], c["frames"])
-        (compare_nan_aware if nans else compare_bytes)(got, want, f"aux planes vs oracle, named codes [{case}]")
+        (compare_nan_aware if nans else compare_exact)(got, want, KEYS, f"aux planes vs oracle, named codes [{case}]")
     if library_powr == 1 or nans:
         named = denoise(*size, c["not_scaled"], c["scaled"], c["half"], c["source"], c["frames"], (), library_powr)
-        compare_bytes(got, named, f"aux planes vs named codes, library_powr {library_powr} [{case}]")
+        compare_exact(got, named, KEYS, f"aux planes vs named codes, library_powr {library_powr} [{case}]")
 
 
 def test_with_prev_pixel_plane(gpu):
@@ -204,9 +122,9 @@ def test_with_prev_pixel_plane(gpu):
     ns, sc = _lists(c)
     size = (c["W"], c["H"])
     a = denoise(*size, c["not_scaled"], c["scaled"], c["half"], "pan", 6)
-    b = denoise(*size, ns, sc, c["half"], "pan", 6, c["names"], prev_pixel=[r["prev_pixel"] for r in a])
-    compare_bytes(b, a, "aux planes + prev_pixel vs named codes by matrix")
-    compare_bytes(b, oracle_named(*size, c["not_scaled"], c["scaled"], c["half"], "pan", 6),
+    b = denoise(*size, ns, sc, c["half"], "pan", 6, c["names"], replay=a)
+    compare_exact(b, a, KEYS, "aux planes + prev_pixel vs named codes by matrix")
+    compare_exact(b, oracle_named(*size, c["not_scaled"], c["scaled"], c["half"], "pan", 6), KEYS,
                   "aux planes + prev_pixel vs oracle")
 
 
@@ -215,8 +133,8 @@ def test_sequence_equals_frames(gpu):
     ns, sc = _lists(c)
     per_frame = denoise(c["W"], c["H"], ns, sc, c["half"], c["source"], c["frames"], c["names"])
     outs, last = denoise(c["W"], c["H"], ns, sc, c["half"], c["source"], c["frames"], c["names"], mode="sequence")
-    compare_bytes(outs, per_frame, "process_sequence outputs vs process_frame", keys=("result",))
-    compare_bytes([last], [per_frame[-1]], "process_sequence state vs process_frame")
+    compare_exact(outs, per_frame, ("result",), "process_sequence outputs vs process_frame")
+    compare_exact([last], [per_frame[-1]], KEYS, "process_sequence state vs process_frame")
 
 
 def test_interior_border_equals_frame(gpu):
@@ -224,7 +142,7 @@ def test_interior_border_equals_frame(gpu):
     ns, sc = _lists(c)
     whole = denoise(c["W"], c["H"], ns, sc, c["half"], c["source"], c["frames"], c["names"])
     split = denoise(c["W"], c["H"], ns, sc, c["half"], c["source"], c["frames"], c["names"], mode="split")
-    compare_bytes(split, whole, "_interior + _border vs process_frame")
+    compare_exact(split, whole, KEYS, "_interior + _border vs process_frame")
 
 
 # ---------------------------------------------------------------- part B ----
@@ -236,4 +154,4 @@ def test_novel_planes_equal_the_composed_oracle(W, H, half, source, gpu):
     want = aux_np.novel_frames(W, H, half, source)
     got = denoise(W, H, aux_np.NOVEL_NOT_SCALED, aux_np.NOVEL_SCALED, half, source, aux_np.NOVEL_FRAMES,
                   aux_np.NOVEL_NAMES)
-    compare_bytes(got, want, f"library vs AuxOracleLoop [{W}x{H} half={half} {source}]")
+    compare_exact(got, want, KEYS, f"library vs AuxOracleLoop [{W}x{H} half={half} {source}]")

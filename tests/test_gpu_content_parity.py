@@ -44,32 +44,24 @@ there (3.3 px/frame on the wall, up to 5.5 on the quad).
 """
 from __future__ import annotations
 
-import numpy as np
 import pytest
 import torch
 
 import bmfr_amd
-import pyoracle
-import ref_run
 import scenes_np
+from parity_harness import Suite, bmfr_cfg, check_tiled_half_inputs
 from ref_configs import REF_CONFIGS
-from seq_util import ALL_KEYS, compare_exact, to_np
+from seq_util import (ALL_KEYS, FUSED_KEYS, TILE_FACTOR, TOL, assert_finite, compare_exact, compare_nan_aware,
+                      rel_l2_finite, to_np, worst_tile)
 
 pytestmark = pytest.mark.gpu
 
 FRAMES = 6
 SEED = 2   # tests/test_scenes_np.py asserts the coverage for this seed
-TOL = 1e-4  # north_star: "within 1e-4 relative L2 of the OpenCL reference" (tests/test_gpu_fast_fit.py)
-TILE_FACTOR = 4.0
-PLANES = ("noisy", "normals", "positions", "albedo")
 CANONICAL = ("s128x80_h13", "s128x80_f13", "s100x72_h16", "s96x64_f16")
 GENERIC = ("s96x64_h7", "s80x64_h12")
 CASES = [(s, n) for s in ("pan", "far", "rand", "clamp") for n in CANONICAL] + \
         [(s, n) for s in ("rand", "clamp") for n in GENERIC]
-# record key -> bmfr_state plane.  (The fused kernel keeps the accept bits in registers -- bmfr_state
-# reports no accept plane -- so they are compared through what they decide: spp and both accumulations.)
-FUSED_KEYS = {"result": "result", "noisy": "noisy_accumulated", "acc": "filtered_accumulated", "spp": "spp",
-              "prev_pixel": "prev_frame_pixel"}
 
 
 def content(scene: str, name: str) -> str:
@@ -77,52 +69,41 @@ def content(scene: str, name: str) -> str:
     return "clamp_nan" if scene == "clamp" and not REF_CONFIGS[name].half_tmp else scene
 
 
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()  # a copy: the generator's planes are read-only
+def frame(case, f):
+    scene, name = case
+    rc = REF_CONFIGS[name]
+    return scenes_np.frame(content(scene, name), rc.width, rc.height, f, SEED)
 
 
-def through_half(a: np.ndarray) -> np.ndarray:
-    return a.astype(np.float16).astype(np.float32)
+# a case is (scene, name); a missing reference build fails
+SUITE = Suite(frame, lambda case: REF_CONFIGS[case[1]], FRAMES, missing_ref=pytest.fail)
 
 
-def bmfr_cfg(rc, **kw) -> bmfr_amd.BmfrConfig:
-    return bmfr_amd.BmfrConfig(image_width=rc.width, image_height=rc.height, not_scaled=rc.not_scaled,
-                               scaled=rc.scaled, use_half_precision_in_tmp_data=rc.half_tmp,
-                               position_limit_squared=rc.position_limit_squared,
-                               normal_limit_squared=rc.normal_limit_squared, **kw)
+def need_ref(name, mode="strict"):
+    SUITE.need_ref((None, name), mode)
 
 
-def _floats(a: np.ndarray):
-    if a.dtype == np.uint16:  # half buffers travel as their bits (seq_util.to_np)
-        return a.view(np.float16)
-    return a if a.dtype.kind == "f" else None
+def ref_frames(scene, name, mode="strict", half_in=False):
+    return SUITE.ref_frames((scene, name), mode, half_in)
 
 
-def compare_nan_aware(got, ref, keys, where=""):
-    """Equal when the NaN positions are the same set and every other element,
-    infinities included, has the same bits."""
-    for f, (g, r) in enumerate(zip(got, ref)):
-        for k in keys:
-            a, b = g[k].reshape(-1), r[k].reshape(-1)
-            assert a.shape == b.shape and a.dtype == b.dtype, (where, f, k, a.shape, b.shape)
-            fa, fb = _floats(a), _floats(b)
-            if fa is None:
-                bad = np.flatnonzero(a != b)
-            else:
-                na, nb = np.isnan(fa), np.isnan(fb)
-                assert (na == nb).all(), f"{where} frame {f} {k}: NaN at {int(na.sum())} vs {int(nb.sum())} places, " \
-                                         f"first difference at {np.flatnonzero(na != nb)[:5]}"
-                bits = {2: np.uint16, 4: np.uint32}[a.dtype.itemsize]
-                bad = np.flatnonzero((a.view(bits) != b.view(bits)) & ~na)
-            assert bad.size == 0, f"{where} frame {f} {k}: {bad.size} of {a.size} differ, first at {bad[:5]}: " \
-                                  f"{a[bad[:5]]} vs {b[bad[:5]]}"
+def oracle_frames(scene, name):
+    return SUITE.oracle_frames((scene, name))
 
 
-def assert_finite(frames, keys, where=""):
-    for f, g in enumerate(frames):
-        for k in keys:
-            v = _floats(g[k])
-            assert v is None or np.isfinite(v).all(), (where, f, k)
+def stage_frames(scene, name, library_powr):
+    return SUITE.stage_frames((scene, name), library_powr)
+
+
+def device_frames(scene, name, half_in=False):
+    """Per frame: (planes on the device, previous camera, jitter)."""
+    return SUITE.device_frames((scene, name), half_in)
+
+
+def fused_frames(scene, name, **options):
+    """The production frame path, frame by frame: one launch per frame, or
+    (profiled: per-kernel events) K1 and K2 as two launches."""
+    return SUITE.kept_fused_frames((scene, name), **options)
 
 
 def compare(scene, got, ref, keys, where):
@@ -131,84 +112,6 @@ def compare(scene, got, ref, keys, where):
     else:
         assert_finite(ref, keys, where + " (reference)")
         compare_exact(got, ref, keys, where)
-
-
-_cache = {}
-
-
-def cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
-
-
-def need_ref(name, mode="strict"):
-    if not ref_run.available(name, mode):
-        pytest.fail(f"reference build {name}_{mode} missing (oracle/build_ref.py)")
-
-
-def ref_frames(scene, name, mode="strict", half_in=False):
-    need_ref(name, mode)
-    rc = REF_CONFIGS[name]
-    return cached((scene, name, "ref", mode, half_in), lambda: scenes_np.run_loop(
-        ref_run.RefLoop(rc, mode), content(scene, name), rc.width, rc.height, FRAMES, SEED, to_device=_dev,
-        sync=torch.cuda.synchronize, prepare=through_half if half_in else None))
-
-
-def oracle_frames(scene, name):
-    rc = REF_CONFIGS[name]
-    cfg = pyoracle.make_cfg(rc.width, rc.height, rc.not_scaled, rc.scaled, rc.half_tmp)
-    return cached((scene, name, "oracle"), lambda: scenes_np.run_loop(
-        pyoracle.OracleLoop(cfg), content(scene, name), rc.width, rc.height, FRAMES, SEED))
-
-
-def stage_frames(scene, name, library_powr):
-    rc = REF_CONFIGS[name]
-    return cached((scene, name, "stages", library_powr), lambda: scenes_np.run_loop(
-        bmfr_amd.StagePipeline(bmfr_cfg(rc, library_powr=library_powr)), content(scene, name), rc.width, rc.height,
-        FRAMES, SEED, to_device=_dev, sync=torch.cuda.synchronize))
-
-
-def device_frames(scene, name, half_in=False):
-    """Per frame: (planes on the device, previous camera, jitter)."""
-    rc = REF_CONFIGS[name]
-
-    def make():
-        out = []
-        for f in range(FRAMES):
-            fr = scenes_np.frame(content(scene, name), rc.width, rc.height, f, SEED)
-            planes = {k: _dev(fr[k].astype(np.float16) if half_in else fr[k]) for k in PLANES}
-            out.append((planes, fr["prev_vp"], fr["jitter"]))
-        return out
-    return cached((scene, name, "device", half_in), make)
-
-
-def fused_state(den, n):
-    f32 = lambda m: torch.empty(m, device="cuda")  # noqa: E731
-    u8 = lambda m: torch.empty(m, dtype=torch.uint8, device="cuda")  # noqa: E731
-    out = {"result": den.copy_output(f32(3 * n))}
-    for k, name in FUSED_KEYS.items():
-        if k != "result":
-            out[k] = den.copy_state(name, u8(n) if k == "spp" else f32((2 if k == "prev_pixel" else 3) * n))
-    torch.cuda.synchronize()
-    return {k: to_np(v).copy() for k, v in out.items()}
-
-
-def fused_frames(scene, name, profiled=False, half_in=False, **kw):
-    """The production frame path, frame by frame: one launch per frame, or
-    (profiled: per-kernel events) K1 and K2 as two launches."""
-    rc = REF_CONFIGS[name]
-
-    def make():
-        den = bmfr_amd.Denoiser(bmfr_cfg(rc, input_half=int(half_in), **kw))
-        if profiled:
-            den.set_profiling(True, capacity=FRAMES, stride=1)
-        out = []
-        for f, (p, vp, jit) in enumerate(device_frames(scene, name, half_in)):
-            den.process_frame(p["noisy"], p["normals"], p["positions"], p["albedo"], vp, jit, f)
-            out.append(fused_state(den, rc.width * rc.height))
-        return out
-    return cached((scene, name, "fused", profiled, half_in, tuple(sorted(kw.items()))), make)
 
 
 def ids(cases):
@@ -254,45 +157,15 @@ HALF_CASES = [(s, n) for s in ("pan", "rand", "clamp") for n in ("s128x80_h13", 
 def test_half_inputs_match_widened_and_reference(scene, name, gpu):
     """Half input planes (the paired 12-byte tap loads) through every accept
     mask and the clamped off-image tap indices."""
-    rc = REF_CONFIGS[name]
     half = fused_frames(scene, name, half_in=True, library_powr=1)
     # the same Denoiser on the widened planes
-    den = bmfr_amd.Denoiser(bmfr_cfg(rc, library_powr=1))
-    wide = []
-    for f, (p, vp, jit) in enumerate(device_frames(scene, name, half_in=True)):
-        w = {k: v.float() for k, v in p.items()}
-        den.process_frame(w["noisy"], w["normals"], w["positions"], w["albedo"], vp, jit, f)
-        wide.append(fused_state(den, rc.width * rc.height))
+    wide = SUITE.fused_frames((scene, name), half_in=True, widen=True, library_powr=1)
     compare(scene, half, wide, tuple(FUSED_KEYS), f"half vs widened[{scene} {name}]")
     compare(scene, half, ref_frames(scene, name, "strict", half_in=True), tuple(FUSED_KEYS),
             f"half vs reference on widened[{scene} {name}]")
     # the half path really read half planes
     f32 = fused_frames(scene, name, library_powr=1)
     assert half[-1]["result"].tobytes() != f32[-1]["result"].tobytes()
-
-
-def rel_l2_finite(a, b, where):
-    """Relative L2 over the elements finite in the reference b; the
-    non-finite positions must coincide."""
-    fa, fb = np.isfinite(a), np.isfinite(b)
-    assert (fa == fb).all(), (where, int((~fa).sum()), int((~fb).sum()))
-    a, b = a[fb].astype(np.float64), b[fb].astype(np.float64)
-    n = np.linalg.norm(b)
-    return float(np.linalg.norm(a - b) / n) if n > 0 else None
-
-
-def worst_tile(frames, ref, W, H):
-    """(worst relative L2, frame, tile x, tile y) over the 32x32 image-aligned
-    tiles of `result`; tiles whose reference norm is zero are skipped."""
-    worst = (0.0, -1, -1, -1)
-    for f, (g, r) in enumerate(zip(frames, ref)):
-        a, b = g["result"].reshape(H, W, 3), r["result"].reshape(H, W, 3)
-        for ty in range(0, H, 32):
-            for tx in range(0, W, 32):
-                e = rel_l2_finite(a[ty:ty + 32, tx:tx + 32], b[ty:ty + 32, tx:tx + 32], (f, tx, ty))
-                if e is not None and e > worst[0]:
-                    worst = (e, f, tx, ty)
-    return worst
 
 
 # (case id, reference configuration, half input planes): the configurations fast_fit supports
@@ -373,68 +246,3 @@ def test_tiled_half_inputs_match_untiled(gx, gy, scene, fast_fit, gpu):
     """Tiled contexts have non-zero plane origins and region-sized planes:
     the paired half tap loads there, against the untiled half-input frame."""
     check_tiled_half_inputs(gx, gy, scene, fast_fit=fast_fit)
-
-
-def check_tiled_half_inputs(gx, gy, scene, split=False, **cfg_kw):
-    """The tiled case: every frame of every tile == the untiled frame bit for
-    bit, the halo report clean.  split: each frame as process_frame_interior,
-    halo exchange, process_frame_border instead of exchange, process_frame.
-    cfg_kw: BmfrConfig keywords of every context, the untiled one included."""
-    from bmfr_amd.tiling import HipCopier, LoopbackTransport, TileGrid, state_planes
-    W, H, halo = 320, 256, 40
-    n = W * H
-    # a halo of 40 covers 6 px of motion (include/bmfr.h: tile_halo - 34): the pan at a fifth of
-    # its speed, 3.3 px/frame on the wall and up to 5.5 on the quad (1.7 x the parallax); rand
-    # moves up to 5.9 px at this size
-    speed = 0.2 if scene == "pan" else 1.0
-    grid = TileGrid(W, H, gx, gy, halo=halo)
-    kw = dict(image_width=W, image_height=H, input_half=1, **cfg_kw)
-    full = bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(**kw))
-    tiles = [bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(tile=grid.tile(r), tile_halo=halo, **kw))
-             for r in range(grid.ranks)]
-    loop, copier = LoopbackTransport(grid), HipCopier()
-    prev = [None] * grid.ranks
-    crossed = [False] * grid.ranks
-    for f in range(FRAMES):
-        fr = scenes_np.frame(scene, W, H, f, SEED, speed=speed)
-        vp, jit = fr["prev_vp"], fr["jitter"]
-        p = {k: _dev(fr[k].astype(np.float16)) for k in PLANES}
-        full.process_frame(p["noisy"], p["normals"], p["positions"], p["albedo"], vp, jit, f)
-        inps = []
-        for d in tiles:
-            cut = scenes_np.frame(scene, W, H, f, SEED, region=d.region, speed=speed)
-            inps.append({k: _dev(cut[k].astype(np.float16)) for k in PLANES})
-        for call in ("process_frame_interior", "process_frame_border") if split else ("process_frame",):
-            if f > 0 and call != "process_frame_interior":
-                loop.exchange_all([state_planes(d) for d in tiles], copier)
-            for r, d in enumerate(tiles):
-                i = inps[r]
-                getattr(d, call)(i["noisy"], i["normals"], i["positions"], i["albedo"], vp, jit, f,
-                                 prev_normals=prev[r]["normals"] if prev[r] else None,
-                                 prev_positions=prev[r]["positions"] if prev[r] else None)
-        prev = inps
-        torch.cuda.synchronize()
-        want = {"result": full.copy_output(torch.empty(3 * n, device="cuda")).view(H, W, 3),
-                "filtered_accumulated": full.copy_state("filtered_accumulated",
-                                                        torch.empty(3 * n, device="cuda")).view(H, W, 3),
-                "noisy_accumulated": full.copy_state("noisy_accumulated",
-                                                     torch.empty(3 * n, device="cuda")).view(H, W, 3)}
-        pp = full.copy_state("prev_frame_pixel", torch.empty(2 * n, device="cuda")).view(H, W, 2).cpu().numpy()
-        assert np.isfinite(to_np(want["result"])).all()
-        for r, d in enumerate(tiles):
-            assert d.halo_status() == 0, (f, r)
-            rx, ry, rw, rh = d.region
-            x, y, w, h = grid.tile(r)
-            for k, v in want.items():
-                t = torch.empty(3 * rw * rh, device="cuda")
-                got = (d.copy_output(t) if k == "result" else d.copy_state(k, t)).view(rh, rw, 3)
-                a = got[y - ry:y - ry + h, x - rx:x - rx + w].contiguous().view(torch.int32)
-                b = v[y:y + h, x:x + w].contiguous().view(torch.int32)
-                assert torch.equal(a, b), (f, r, k, int((a != b).sum()))
-            if f > 0:  # pixels of this tile whose reprojection lands in the image, in the other tile
-                q = pp[y:y + h, x:x + w]
-                inside = (q[..., 0] >= 0) & (q[..., 0] < W) & (q[..., 1] >= 0) & (q[..., 1] < H)
-                own = (q[..., 0] >= x) & (q[..., 0] < x + w) & (q[..., 1] >= y) & (q[..., 1] < y + h)
-                crossed[r] = crossed[r] or bool((inside & ~own).any())
-    if scene == "pan":
-        assert all(crossed), crossed

@@ -23,41 +23,19 @@ import torch
 
 import bmfr_amd
 import ref_run
+from parity_harness import fused_state, rel_l2, same_bits
 from ref_configs import FULL_REF_CONFIGS
+from seq_util import PLANES, TOL
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4  # north_star: "within 1e-4 relative L2 of the OpenCL reference"
-
-
-def rel_l2(a: torch.Tensor, b: torch.Tensor) -> float:
-    a, b = a.double().reshape(-1), b.double().reshape(-1)
-    return float(torch.linalg.norm(a - b) / torch.linalg.norm(b))
-
-
-def same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    if a.dtype == torch.float32:
-        a, b = a.view(torch.int32), b.view(torch.int32)
-    return torch.equal(a, b)
 
 
 def frames_of(W, H, n, **kw):
     cfg = bmfr_amd.BmfrConfig(image_width=W, image_height=H, fast_fit=1, **kw)
     frames = [bmfr_amd.synth_frame_device(W, H, f) for f in range(n)]
     if kw.get("input_half"):  # half3 input planes (the f32 render rounded to nearest)
-        frames = [{k: (v.half() if k in ("noisy", "normals", "positions", "albedo") else v) for k, v in fr.items()}
-                  for fr in frames]
+        frames = [{k: (v.half() if k in PLANES else v) for k, v in fr.items()} for fr in frames]
     return cfg, frames
-
-
-def state(den, n):
-    return {
-        "result": den.copy_output(torch.empty(3 * n, device="cuda")),
-        "acc": den.copy_state("filtered_accumulated", torch.empty(3 * n, device="cuda")),
-        "noisy": den.copy_state("noisy_accumulated", torch.empty(3 * n, device="cuda")),
-        "spp": den.copy_state("spp", torch.empty(n, dtype=torch.uint8, device="cuda")),
-        "prev_pixel": den.copy_state("prev_frame_pixel", torch.empty(2 * n, device="cuda")),
-    }
 
 
 def run_frames(cfg, frames, profiled=False):
@@ -70,7 +48,7 @@ def run_frames(cfg, frames, profiled=False):
         vp, _ = bmfr_amd.synth_camera(W, H, max(f - 1, 0))
         _, jit = bmfr_amd.synth_camera(W, H, f)
         den.process_frame(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"], vp, jit, f)
-        out.append(state(den, W * H))
+        out.append(fused_state(den, W * H, host=False))
     torch.cuda.synchronize()
     return out
 
@@ -125,7 +103,7 @@ def test_fast_fit_within_tolerance_of_reference(name, n, gpu, parity_log):
         vp, _ = bmfr_amd.synth_camera(W, H, max(f - 1, 0))
         _, jit = bmfr_amd.synth_camera(W, H, f)
         den.process_frame(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"], vp, jit, f)
-        got = state(den, W * H)
+        got = fused_state(den, W * H, host=False)
         for m, rl in refs.items():
             rec = {}
             rl.upload(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"])
@@ -162,7 +140,7 @@ def test_bench_configuration_within_tolerance_of_reference(gpu, parity_log):
         vp, _ = bmfr_amd.synth_camera(W, H, max(f - 1, 0))
         _, jit = bmfr_amd.synth_camera(W, H, f)
         den.process_frame(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"], vp, jit, f)
-        got = state(den, W * H)
+        got = fused_state(den, W * H, host=False)
         rec = {}
         ref.upload(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"])
         ref.run_stages(vp, jit, f, record=rec)
@@ -194,13 +172,13 @@ def test_cfg5_timed_configuration_within_tolerance_of_reference(gpu, parity_log)
     worst = {m: 0.0 for m in refs}
     for f in range(rc.frames):
         fr = bmfr_amd.synth_frame_device(W, H, f, seed=rc.seed)
-        h = {k: fr[k].half() for k in ("noisy", "normals", "positions", "albedo")}
+        h = {k: fr[k].half() for k in PLANES}
         w = {k: v.float() for k, v in h.items()}
         del fr
         vp, _ = bmfr_amd.synth_camera(W, H, max(f - 1, 0))
         _, jit = bmfr_amd.synth_camera(W, H, f)
         den.process_frame(h["noisy"], h["normals"], h["positions"], h["albedo"], vp, jit, f)
-        got = state(den, W * H)
+        got = fused_state(den, W * H, host=False)
         for m, rl in refs.items():
             rec = {}
             rl.upload(w["noisy"], w["normals"], w["positions"], w["albedo"])

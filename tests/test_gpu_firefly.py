@@ -21,13 +21,12 @@ from bmfr_amd.tiling import LoopbackTransport, TileGrid, region_slice
 import firefly_np as fn
 import prepare_np as pn
 import scenes_np
+from parity_harness import state_snapshot
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 W, H = 128, 80
-STATE = (("noisy_accumulated", 3, torch.float32), ("spp", 1, torch.uint8), ("filtered_accumulated", 3, torch.float32),
-         ("result", 3, torch.float32), ("prev_frame_pixel", 2, torch.float32))
 # radius, threshold, floor, replace_nonfinite: every value of each, all together
 RULES = list(itertools.product((1, 2), (1.0, 2.0, 4.0), (0.0, 0.05), (1, 0)))
 
@@ -54,12 +53,6 @@ def _plane(a: np.ndarray, offset_bytes: int = 0) -> torch.Tensor:
     assert big.data_ptr() % 16 == 0
     big[k:].copy_(t)
     return big[k:]
-
-
-def _state(den) -> dict:
-    n = den.sizes.region_width * den.sizes.region_height
-    return {name: den.copy_state(name, torch.empty(n * ch, dtype=dt, device="cuda")).cpu().numpy()
-            for name, ch, dt in STATE}
 
 
 class _Raw:
@@ -214,14 +207,14 @@ def test_call_between_two_frames_changes_no_state(gpu):
         for den in (A, B):
             den.process_frame(d["noisy"], d["normals"], d["positions"], d["albedo"], fr["prev_vp"], fr["jitter"], f)
         if f == 0:
-            before, status = _state(A), A.frame_status()
+            before, status = state_snapshot(A), A.frame_status()
             A.suppress_fireflies(d["noisy"], radius=2, stats=torch.zeros(2, dtype=torch.int32, device="cuda"))
             torch.cuda.synchronize()
-            after = _state(A)
+            after = state_snapshot(A)
             assert A.frame_status() == status == 0
             for name in before:
                 _same(after[name], before[name], name)
-    a, b = _state(A), _state(B)
+    a, b = state_snapshot(A), state_snapshot(B)
     for name in a:
         _same(a[name], b[name], ("frame 1", name))
     assert A.frame_status() == 0
@@ -342,7 +335,7 @@ def test_process_gbuffer_with_firefly(half, gpu):
                         prev_normals=p["prev_normals_moved"] if f else None,
                         prev_positions=p["prev_positions_moved"] if f else None,
                         prev_pixel=p["prev_pixel"] if f else None)
-        a, b, c, d = _state(A), _state(B), _state(C0), _state(D)
+        a, b, c, d = state_snapshot(A), state_snapshot(B), state_snapshot(C0), state_snapshot(D)
         for name in b:
             _same(a[name], b[name], (f, name, "firefly"))
             _same(d[name], c[name], (f, name, "firefly=None"))

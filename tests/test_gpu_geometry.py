@@ -37,119 +37,26 @@ import torch
 import aux_np
 import bmfr_amd
 import geometry_util as gu
-import ref_run
 import scenes_np
 import shape_util
 from bmfr_amd.tiling import HipCopier, LoopbackTransport, TileGrid, state_planes
 from geometry_util import CANONICAL, CANONICAL_HALF, GENERIC, NAMES
+from parity_harness import Suite, bmfr_cfg, fused_state, to_device
 from ref_configs import GEOMETRY_REF_CONFIGS, GEOMETRY_SCENE
-from seq_util import ALL_KEYS, compare_exact, to_np
-from test_gpu_content_parity import TILE_FACTOR, TOL, rel_l2_finite, through_half
-from test_gpu_motion_input import GARBAGE_JITTER, NAN_VP
-from test_gpu_shapes import compare_bytes, fused_state
+from seq_util import ALL_KEYS, FUSED_KEYS, PLANES, TILE_FACTOR, TOL, compare_exact, rel_l2_finite, to_np
 
 pytestmark = pytest.mark.gpu
 
-PLANES = ("noisy", "normals", "positions", "albedo")
-_cache = {}
-
-
-def cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()  # a copy: the generator's planes are read-only
-
-
-def bmfr_cfg(rc, lists=None, **kw) -> bmfr_amd.BmfrConfig:
-    not_scaled, scaled = lists or (rc.not_scaled, rc.scaled)
-    return bmfr_amd.BmfrConfig(image_width=rc.width, image_height=rc.height, not_scaled=tuple(not_scaled),
-                               scaled=tuple(scaled), use_half_precision_in_tmp_data=rc.half_tmp, **rc.knobs(), **kw)
-
-
-def ref_frames(name, mode="strict", half_in=False):
-    if not ref_run.available(name, mode):
-        pytest.skip(f"reference build {name}_{mode} missing (oracle/build_ref.py)")
-    rc = GEOMETRY_REF_CONFIGS[name]
-    return cached((name, "ref", mode, half_in), lambda: gu.run_loop(
-        ref_run.RefLoop(rc, mode), name, to_device=_dev, sync=torch.cuda.synchronize,
-        prepare=through_half if half_in else None))
-
-
-def stage_frames(name, library_powr):
-    rc = GEOMETRY_REF_CONFIGS[name]
-    return cached((name, "stages", library_powr), lambda: gu.run_loop(
-        bmfr_amd.StagePipeline(bmfr_cfg(rc, library_powr=library_powr)), name, to_device=_dev,
-        sync=torch.cuda.synchronize))
-
-
-def device_frames(name, half_in=False, aux_names=()):
-    """Per frame: (planes on the device -- "aux": the planes of aux_names --,
-    previous camera, jitter)."""
-    rc = GEOMETRY_REF_CONFIGS[name]
-
-    def make():
-        out = []
-        for f in range(rc.frames):
-            fr = gu.frame(name, f)
-            d = {k: _dev(fr[k].astype(np.float16) if half_in else fr[k]) for k in PLANES}
-            d["aux"] = [None if p is None else _dev(p) for p in
-                        aux_np.aux_planes(aux_names, fr["normals"], fr["positions"], fr["albedo"], rc.width, rc.height)]
-            out.append((d, fr["prev_vp"], fr["jitter"]))
-        return out
-    return cached((name, "device", half_in, tuple(aux_names)), make)
-
-
-def fused_frames(name, launches=0, profiled=False, half_in=False, widen=False, aux=False, mode="frame", replay=None,
-                 **kw):
-    """The Denoiser over the configuration's frames -> per-frame output and
-    state.  launches: debug_frame_launches; profiled: per-kernel events (K1
-    and K2 as two launches); half_in: half input planes (widen: the same
-    values as f32, into an f32 context); aux: the list of shape_util.aux_case_of
-    with its planes; mode: "frame", "split" (_interior + _border) or
-    "sequence" (one process_sequence call -> (per-frame outputs, last state));
-    replay: the per-frame records of another run, whose prev_frame_pixel plane
-    each frame from 1 on is fed under a NaN camera; kw: BmfrConfig keywords.
-    Every run asserts frame_status OK."""
-    rc = GEOMETRY_REF_CONFIGS[name]
-    n = rc.width * rc.height
-    not_scaled, scaled, aux_names = shape_util.aux_case_of(rc) if aux else (rc.not_scaled, rc.scaled, ())
-    den = bmfr_amd.Denoiser(bmfr_cfg(rc, (not_scaled, scaled), input_half=int(half_in and not widen), **kw))
-    den.debug_frame_launches(launches)
-    if profiled:
-        den.set_profiling(True, capacity=rc.frames, stride=1)
-    frames = device_frames(name, half_in, aux_names)
-    if widen:
-        frames = [({k: (v.float() if k in PLANES else v) for k, v in d.items()}, vp, jit) for d, vp, jit in frames]
-    if mode == "sequence":
-        outs = [torch.empty(3 * n, device="cuda") for _ in frames]
-        den.process_sequence([d for d, _, _ in frames], [(vp, jit) for _, vp, jit in frames], 0, outputs=outs)
-        torch.cuda.synchronize()
-        assert den.frame_status() == 0, (name, den.frame_status())
-        return [{"result": to_np(o).copy()} for o in outs], fused_state(den, n)
-    out = []
-    for f, (d, vp, jit) in enumerate(frames):
-        plane = None
-        if replay is not None:
-            vp, jit = NAN_VP, GARBAGE_JITTER
-            # frame 0 ignores the plane
-            plane = torch.full((2 * n,), float("nan"), device="cuda") if f == 0 else _dev(replay[f]["prev_pixel"])
-        args = (d["noisy"], d["normals"], d["positions"], d["albedo"], vp, jit, f)
-        if mode == "split":
-            den.process_frame_interior(*args, aux=d["aux"], prev_pixel=plane)
-            den.process_frame_border(*args, aux=d["aux"], prev_pixel=plane)
-        else:
-            den.process_frame(*args, aux=d["aux"], prev_pixel=plane)
-        out.append(fused_state(den, n))
-        assert den.frame_status() == 0, (name, f, den.frame_status())
-    return out
+KEYS = tuple(FUSED_KEYS)
+# a case is a configuration name; a missing reference build skips.  fused_frames: parity_harness.fused_frames
+# over the configuration's frames (aux: the list of shape_util.aux_case_of with its planes); kept_frames: run once
+SUITE = Suite(gu.frame, GEOMETRY_REF_CONFIGS.get, missing_ref=pytest.skip)
+ref_frames, stage_frames = SUITE.ref_frames, SUITE.stage_frames
+fused_frames, kept_frames = SUITE.fused_frames, SUITE.kept_fused_frames
 
 
 def plain_frames(name, library_powr=0):
-    return cached((name, "fused", library_powr), lambda: fused_frames(name, library_powr=library_powr))
+    return kept_frames(name, library_powr=library_powr)
 
 
 # ------------------------------------------------------- every configuration ----
@@ -168,7 +75,7 @@ def test_stage_kernels_match_oracle_bitwise(name, gpu):
 @pytest.mark.parametrize("library_powr", [0, 1])
 @pytest.mark.parametrize("name", NAMES)
 def test_fused_frame_matches_stages_bitwise(name, library_powr, gpu):
-    compare_bytes(plain_frames(name, library_powr), stage_frames(name, library_powr),
+    compare_exact(plain_frames(name, library_powr), stage_frames(name, library_powr), KEYS,
                   f"process_frame vs stages[{name} powr {library_powr}]")
 
 
@@ -181,10 +88,10 @@ def test_one_launch_two_launches_and_profiled_agree(name, gpu):
     st = stage_frames(name, 0)
     one, two = fused_frames(name, launches=1), fused_frames(name, launches=2)
     prof = fused_frames(name, profiled=True)
-    compare_bytes(one, two, f"one launch vs two[{name}]")
-    compare_bytes(prof, two, f"profiled vs two launches[{name}]")
-    compare_bytes(one, st, f"one launch vs stages[{name}]")
-    compare_bytes(two, st, f"two launches vs stages[{name}]")
+    compare_exact(one, two, KEYS, f"one launch vs two[{name}]")
+    compare_exact(prof, two, KEYS, f"profiled vs two launches[{name}]")
+    compare_exact(one, st, KEYS, f"one launch vs stages[{name}]")
+    compare_exact(two, st, KEYS, f"two launches vs stages[{name}]")
 
 
 @pytest.mark.parametrize("schedule", ["fused", "streams"])
@@ -196,8 +103,8 @@ def test_sequence_equals_frames(name, schedule, gpu, monkeypatch):
         monkeypatch.delenv("BMFR_SEQUENCE", raising=False)
     per_frame = plain_frames(name)
     outs, last = fused_frames(name, mode="sequence")
-    compare_bytes(outs, per_frame, f"process_sequence outputs vs process_frame[{name}]", keys=("result",))
-    compare_bytes([last], [per_frame[-1]], f"process_sequence state vs process_frame[{name}]")
+    compare_exact(outs, per_frame, ("result",), f"process_sequence outputs vs process_frame[{name}]")
+    compare_exact([last], [per_frame[-1]], KEYS, f"process_sequence state vs process_frame[{name}]")
 
 
 # -------------------------------------- canonical lists with half tmp_data ----
@@ -205,17 +112,17 @@ def test_sequence_equals_frames(name, schedule, gpu, monkeypatch):
 def test_half_inputs_match_widened(name, gpu):
     """Half input planes: the 12-byte load of two half3 pixels at an odd pixel
     index, rows of odd stride in the 6-byte planes."""
-    half = cached((name, "half"), lambda: fused_frames(name, half_in=True, library_powr=1))
+    half = kept_frames(name, half_in=True, library_powr=1)
     wide = fused_frames(name, half_in=True, widen=True, library_powr=1)
-    compare_bytes(half, wide, f"half vs widened[{name}]")
+    compare_exact(half, wide, KEYS, f"half vs widened[{name}]")
     # the half path really read half planes
     assert half[-1]["result"].tobytes() != plain_frames(name, 1)[-1]["result"].tobytes()
 
 
 @pytest.mark.parametrize("name", CANONICAL_HALF)
 def test_half_inputs_match_reference_on_widened(name, gpu):
-    half = cached((name, "half"), lambda: fused_frames(name, half_in=True, library_powr=1))
-    compare_bytes(half, ref_frames(name, "strict", half_in=True), f"half vs reference on widened[{name}]")
+    half = kept_frames(name, half_in=True, library_powr=1)
+    compare_exact(half, ref_frames(name, "strict", half_in=True), KEYS, f"half vs reference on widened[{name}]")
 
 
 @pytest.mark.parametrize("half_in", [False, True], ids=["f32_in", "half_in"])
@@ -223,9 +130,9 @@ def test_half_inputs_match_reference_on_widened(name, gpu):
 def test_plane_reading_k1_replays_projection(name, half_in, gpu):
     """A context fed the prev_frame_pixel plane another context computed, a
     NaN camera matrix and a garbage pixel offset reproduces it."""
-    want = plain_frames(name) if not half_in else cached((name, "half0"), lambda: fused_frames(name, half_in=True))
+    want = kept_frames(name, half_in=half_in)
     got = fused_frames(name, half_in=half_in, replay=want)
-    compare_bytes(got, want, f"prev_pixel replay vs projection[{name}]")
+    compare_exact(got, want, KEYS, f"prev_pixel replay vs projection[{name}]")
 
 
 # --------------------------------------------------------- the generic lists ----
@@ -239,7 +146,7 @@ def test_aux_kernel_equals_named(name, library_powr, gpu):
     for k, nm in enumerate(aux_names):  # plane k holds the code it replaced
         if nm is not None:
             assert (rc.not_scaled + rc.scaled)[codes.index(aux_np.AUX0 + k)] == aux_np.CODE_OF[nm]
-    compare_bytes(fused_frames(name, aux=True, library_powr=library_powr), plain_frames(name, library_powr),
+    compare_exact(fused_frames(name, aux=True, library_powr=library_powr), plain_frames(name, library_powr), KEYS,
                   f"aux vs named[{name} powr {library_powr}]")
 
 
@@ -247,7 +154,8 @@ def test_aux_kernel_equals_named(name, library_powr, gpu):
 @pytest.mark.parametrize("name", GENERIC)
 def test_interior_border_equals_frame(name, aux, gpu):
     whole = fused_frames(name, aux=True) if aux else plain_frames(name)
-    compare_bytes(fused_frames(name, aux=aux, mode="split"), whole, f"_interior + _border vs process_frame[{name}]")
+    compare_exact(fused_frames(name, aux=aux, mode="split"), whole, KEYS,
+                  f"_interior + _border vs process_frame[{name}]")
 
 
 # ----------------------------------------------------------------------- tiled ----
@@ -298,12 +206,12 @@ def test_tiled_matches_untiled(name, half_in, case, gpu):
     for f in range(rc.frames):
         fr = scenes_np.frame(GEOMETRY_SCENE, W, H, f, rc.seed, still=still)
         vp, jit = fr["prev_vp"], fr["jitter"]
-        p = {k: _dev(cut(fr[k])) for k in PLANES}
+        p = {k: to_device(cut(fr[k])) for k in PLANES}
         full.process_frame(p["noisy"], p["normals"], p["positions"], p["albedo"], vp, jit, f)
         inps = []
         for d in tiles:
             part = scenes_np.frame(GEOMETRY_SCENE, W, H, f, rc.seed, region=d.region, still=still)
-            inps.append({k: _dev(cut(part[k])) for k in PLANES})
+            inps.append({k: to_device(cut(part[k])) for k in PLANES})
         if f > 0:
             loop.exchange_all([state_planes(d) for d in tiles], copier)
         for r, d in enumerate(tiles):
@@ -350,7 +258,7 @@ def test_fast_fit_within_tolerance(name, gpu, parity_log):
     print(f"{where}: worst frame vs strict {max(e_fast):.3e} (frame {int(np.argmax(e_fast))}), the reference's "
           f"builds {max(builds):.3e}; per frame {['%.2e' % e for e in e_fast]} / {['%.2e' % e for e in builds]}")
     # the fit does not feed these
-    compare_bytes(fast, strict, where, keys=("noisy", "spp", "prev_pixel"))
+    compare_exact(fast, strict, ("noisy", "spp", "prev_pixel"), where)
     assert all(np.isfinite(g["result"]).all() and np.isfinite(g["acc"]).all() for g in fast)
     # a frame that misses is a known miss (a strict xfail with both figures, like KNOWN_TILE_MISS of
     # tests/test_gpu_content_parity.py) only within TILE_FACTOR times the builds' distance on that frame,

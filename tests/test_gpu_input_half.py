@@ -7,21 +7,16 @@ planes widened to f32 -- every frame, output and temporal state.  The f32
 path itself is pinned to the reference kernels by test_gpu_parity.py."""
 from __future__ import annotations
 
-import numpy as np
 import pytest
 import torch
 
 import bmfr_amd
+from parity_harness import same_bits
+from seq_util import PLANES
 
 pytestmark = pytest.mark.gpu
 
 FRAMES = 6
-PLANES = ("noisy", "normals", "positions", "albedo")
-
-
-def _bits(t: torch.Tensor) -> np.ndarray:
-    return t.cpu().numpy().view(np.uint32)
-
 
 @pytest.mark.parametrize("fast_fit", [0, 1])
 @pytest.mark.parametrize("W,H,scaled,half_tmp", [
@@ -49,18 +44,18 @@ def test_half_inputs_match_widened_f32(W, H, scaled, half_tmp, fast_fit, gpu):
         den_f.process_frame(w["noisy"], w["normals"], w["positions"], w["albedo"], vp, jit, f)
         out_h = den_h.copy_output(torch.empty(n, device="cuda"))
         out_f = den_f.copy_output(torch.empty(n, device="cuda"))
-        assert np.array_equal(_bits(out_h), _bits(out_f)), f"frame {f}: output differs"
+        assert same_bits(out_h, out_f), f"frame {f}: output differs"
         for name in ("noisy_accumulated", "filtered_accumulated"):
             a = den_h.copy_state(name, torch.empty(n, device="cuda"))
             b = den_f.copy_state(name, torch.empty(n, device="cuda"))
-            assert np.array_equal(_bits(a), _bits(b)), f"frame {f}: {name} differs"
+            assert same_bits(a, b), f"frame {f}: {name} differs"
     # The half path really read half planes: the widened-f32 result differs
     # from the result on the original f32 planes.
     den_o = bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(**base))
     fr = bmfr_amd.synth_frame_device(W, H, 0)
     vp, jit = bmfr_amd.synth_camera(W, H, 0)
     den_o.process_frame(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"], vp, jit, 0)
-    assert not np.array_equal(_bits(den_o.copy_output(torch.empty(n, device="cuda"))), _bits(out_h))
+    assert not same_bits(den_o.copy_output(torch.empty(n, device="cuda")), out_h)
 
 
 def test_half_inputs_rejected_where_unsupported(gpu):

@@ -30,19 +30,14 @@ parity log as knobs_<config>.
 """
 from __future__ import annotations
 
-import numpy as np
 import pytest
 import torch
 
 import bmfr_amd
 import knob_util
-import pyoracle
-import ref_run
+from parity_harness import Suite, bmfr_cfg, check_tiled_half_inputs, fused_state
 from ref_configs import KNOB_REF_CONFIGS, knob_set_of
-from seq_util import ALL_KEYS, compare_exact, to_np
-from test_gpu_content_parity import (FUSED_KEYS, PLANES, TILE_FACTOR, TOL, _dev, assert_finite, cached,
-                                     check_tiled_half_inputs, fused_state, need_ref, rel_l2_finite, through_half)
-from test_gpu_motion_input import GARBAGE_JITTER, NAN_VP
+from seq_util import ALL_KEYS, FUSED_KEYS, TILE_FACTOR, TOL, assert_finite, compare_exact, rel_l2_finite, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -53,64 +48,16 @@ PLANE_NAMES = ["k_tight_128x80_h13", "k_ends_100x72_h16"]
 FAST_NAMES = [n for n in NAMES if n != "k_loose_96x64_h7" and knob_set_of(n) != "lit"]
 
 
-def bmfr_cfg(rc, **kw) -> bmfr_amd.BmfrConfig:
-    return bmfr_amd.BmfrConfig(image_width=rc.width, image_height=rc.height, not_scaled=rc.not_scaled,
-                               scaled=rc.scaled, use_half_precision_in_tmp_data=rc.half_tmp, **rc.knobs(), **kw)
-
-
 def compare(got, ref, keys, where):
     assert_finite(ref, keys, where + " (reference)")
-    assert len(got) == len(ref), (where, len(got), len(ref))
-    compare_exact(got, ref, keys, where)
+    compare_exact(got, ref, keys, where)  # the frame counts included
 
 
-def ref_frames(name, mode="strict", half_in=False):
-    need_ref(name, mode)
-    return cached((name, "ref", mode, half_in), lambda: knob_util.run_loop(
-        ref_run.RefLoop(KNOB_REF_CONFIGS[name], mode), name, to_device=_dev, sync=torch.cuda.synchronize,
-        prepare=through_half if half_in else None))
-
-
-def oracle_frames(name):
-    rc = KNOB_REF_CONFIGS[name]
-    cfg = pyoracle.make_cfg(rc.width, rc.height, rc.not_scaled, rc.scaled, rc.half_tmp, **rc.knobs())
-    return cached((name, "oracle"), lambda: knob_util.run_loop(pyoracle.OracleLoop(cfg), name))
-
-
-def stage_frames(name, library_powr):
-    rc = KNOB_REF_CONFIGS[name]
-    return cached((name, "stages", library_powr), lambda: knob_util.run_loop(
-        bmfr_amd.StagePipeline(bmfr_cfg(rc, library_powr=library_powr)), name, to_device=_dev,
-        sync=torch.cuda.synchronize))
-
-
-def device_frames(name, half_in=False):
-    """Per frame: (planes on the device, previous camera, jitter)."""
-    def make():
-        out = []
-        for f in range(KNOB_REF_CONFIGS[name].frames):
-            fr = knob_util.frame(name, f)
-            planes = {k: _dev(fr[k].astype(np.float16) if half_in else fr[k]) for k in PLANES}
-            out.append((planes, fr["prev_vp"], fr["jitter"]))
-        return out
-    return cached((name, "device", half_in), make)
-
-
-def fused_frames(name, profiled=False, half_in=False, **kw):
-    """The production frame path, frame by frame: one launch per frame, or
-    (profiled: per-kernel events) K1 and K2 as two launches."""
-    rc = KNOB_REF_CONFIGS[name]
-
-    def make():
-        den = bmfr_amd.Denoiser(bmfr_cfg(rc, input_half=int(half_in), **kw))
-        if profiled:
-            den.set_profiling(True, capacity=rc.frames, stride=1)
-        out = []
-        for f, (p, vp, jit) in enumerate(device_frames(name, half_in)):
-            den.process_frame(p["noisy"], p["normals"], p["positions"], p["albedo"], vp, jit, f)
-            out.append(fused_state(den, rc.width * rc.height))
-        return out
-    return cached((name, "fused", profiled, half_in, tuple(sorted(kw.items()))), make)
+# a case is a configuration name; a missing reference build fails
+SUITE = Suite(knob_util.frame, KNOB_REF_CONFIGS.get, missing_ref=pytest.fail)
+need_ref, ref_frames, oracle_frames, stage_frames = (SUITE.need_ref, SUITE.ref_frames, SUITE.oracle_frames,
+                                                     SUITE.stage_frames)
+device_frames, fused_frames = SUITE.device_frames, SUITE.kept_fused_frames
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -153,15 +100,9 @@ def test_fused_frame_matches_stages(name, library_powr, gpu, monkeypatch):
 
 @pytest.mark.parametrize("name", HALF_NAMES)
 def test_half_inputs_match_widened_and_reference(name, gpu):
-    rc = KNOB_REF_CONFIGS[name]
     keys = tuple(FUSED_KEYS)
     half = fused_frames(name, half_in=True, library_powr=1)
-    den = bmfr_amd.Denoiser(bmfr_cfg(rc, library_powr=1))  # the same Denoiser on the widened planes
-    wide = []
-    for f, (p, vp, jit) in enumerate(device_frames(name, half_in=True)):
-        w = {k: v.float() for k, v in p.items()}
-        den.process_frame(w["noisy"], w["normals"], w["positions"], w["albedo"], vp, jit, f)
-        wide.append(fused_state(den, rc.width * rc.height))
+    wide = SUITE.fused_frames(name, half_in=True, widen=True, library_powr=1)  # the same Denoiser on the widened planes
     compare(half, wide, keys, f"half vs widened[{name}]")
     compare(half, ref_frames(name, "strict", half_in=True), keys, f"half vs reference on widened[{name}]")
     # the half path really read half planes
@@ -172,19 +113,9 @@ def test_half_inputs_match_widened_and_reference(name, gpu):
 def test_plane_reading_k1_replays_projection(name, gpu):
     """The pattern of tests/test_gpu_motion_input.py: the *_plane kernels are
     translation units of their own and read the same Params."""
-    rc = KNOB_REF_CONFIGS[name]
-    n = rc.width * rc.height
     first = fused_frames(name, library_powr=0)
     compare(first, stage_frames(name, 0), tuple(FUSED_KEYS), f"one launch vs stages[{name}]")
-    den = bmfr_amd.Denoiser(bmfr_cfg(rc))
-    nan_plane = torch.full((2 * n,), float("nan"), device="cuda")  # frame 0 ignores the plane
-    got = []
-    for f, (p, _, _) in enumerate(device_frames(name)):
-        plane = nan_plane if f == 0 else torch.from_numpy(first[f]["prev_pixel"].copy()).cuda()
-        den.process_frame(p["noisy"], p["normals"], p["positions"], p["albedo"], NAN_VP, GARBAGE_JITTER, f,
-                          prev_pixel=plane)
-        got.append(fused_state(den, n))
-    assert den.frame_status() == 0
+    got = SUITE.fused_frames(name, replay=first)  # a NaN camera, first's prev_frame_pixel plane from frame 1 on
     compare(got, first, tuple(FUSED_KEYS), f"by plane vs by matrix[{name}]")
 
 

@@ -21,15 +21,13 @@ import torch
 import bmfr_amd
 from bmfr_amd import _build, _lib
 from bmfr_amd.tiling import NativeExchange, TileGrid, process_frame_tiled, region_slice
-from motion_util import PLANES, bad_entries, quantise, scene_frame, translated
+from motion_util import REACH_SIZE, bad_entries, quantise, scene_frame, shifted, translated
+from parity_harness import STATE, state_snapshot
+from seq_util import GARBAGE_JITTER, NAN_VP, PLANES
 
 pytestmark = pytest.mark.gpu
 
 FRAMES = 18          # all 16 block-grid shifts and the wrap
-NAN_VP = [float("nan")] * 16
-GARBAGE_JITTER = [float("nan"), 1e30]
-STATE = (("noisy_accumulated", 3, torch.float32), ("spp", 1, torch.uint8), ("filtered_accumulated", 3, torch.float32),
-         ("result", 3, torch.float32), ("prev_frame_pixel", 2, torch.float32))
 
 # name -> (BmfrConfig keywords, how context B runs its frames)
 CONFIGS = {
@@ -65,9 +63,7 @@ def _dev(fr: dict, half: bool) -> dict:
 
 def _state(den, names=STATE) -> dict:
     """The named state planes of the last frame, as bytes."""
-    n = den.sizes.region_width * den.sizes.region_height
-    return {name: den.copy_state(name, torch.empty(n * ch, dtype=dt, device="cuda")).cpu().numpy().tobytes()
-            for name, ch, dt in names}
+    return {name: a.tobytes() for name, a in state_snapshot(den, names).items()}
 
 
 def _frozen(kw: dict):
@@ -216,7 +212,7 @@ def test_reach_exceeded_through_planes(dx, gpu):
     shifted camera sends the same taps past the same tiles' valid state, so
     the same tiles report BMFR_ERROR_HALO_EXCEEDED with the same overshoot as
     tiles driven by the matrix."""
-    from test_gpu_reach import HALO, H, W, shifted
+    W, H, HALO = REACH_SIZE
     grid = TileGrid(W, H, 2, 2, halo=HALO)
     full = bmfr_amd.Denoiser(bmfr_amd.BmfrConfig(image_width=W, image_height=H))
     by_matrix, xm = _tiled_contexts(W, H, grid, HALO)

@@ -20,12 +20,13 @@ from __future__ import annotations
 import dataclasses
 
 import pytest
-import torch
 
 import bmfr_amd
 import ref_run
+from fullsize_util import hip_cfg
+from parity_harness import assert_same, fused_state
 from ref_configs import REF_CONFIGS
-from test_gpu_reference_fullsize import assert_same, hip_cfg
+from seq_util import PLANES
 
 pytestmark = pytest.mark.gpu
 
@@ -57,7 +58,7 @@ def test_pair_taps_at_plane_ends_match_reference(gpu):
     # the fix-up supplies (spp grows there)
     fr = bmfr_amd.synth_frame_device(W, H, 0, seed=rc.seed)
     for f, pt in enumerate(points):
-        half = {k: fr[k].half() for k in ("noisy", "normals", "positions", "albedo")}
+        half = {k: fr[k].half() for k in PLANES}
         wide = {k: v.float() for k, v in half.items()}
         if pt is None:
             vp, jit = bmfr_amd.synth_camera(W, H, 0)
@@ -68,13 +69,7 @@ def test_pair_taps_at_plane_ends_match_reference(gpu):
         ref.run_stages(vp, jit, f, record=rec)
         ref.swap()
         den.process_frame(half["noisy"], half["normals"], half["positions"], half["albedo"], vp, jit, f)
-        got = {
-            "result": den.copy_output(torch.empty(3 * n, device="cuda")),
-            "acc": den.copy_state("filtered_accumulated", torch.empty(3 * n, device="cuda")),
-            "noisy": den.copy_state("noisy_accumulated", torch.empty(3 * n, device="cuda")),
-            "spp": den.copy_state("spp", torch.empty(n, dtype=torch.uint8, device="cuda")),
-            "prev_pixel": den.copy_state("prev_frame_pixel", torch.empty(2 * n, device="cuda")),
-        }
+        got = fused_state(den, n, host=False)
         for k, v in got.items():
             assert_same(v, rec[k], f"frame {f} (taps at {pt}) {k}")
         if pt is not None:

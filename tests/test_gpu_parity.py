@@ -21,60 +21,26 @@ from __future__ import annotations
 
 import numpy as np
 import pytest
-import torch
 
 import bmfr_amd
-import pyoracle
-import ref_run
+from parity_harness import Suite, bmfr_cfg, fused_state, to_device
 from ref_configs import REF_CONFIGS
-from seq_util import (ALL_KEYS, EXACT_KEYS, POWR_KEYS, compare_exact, rel_l2, run_loop)
+from seq_util import ALL_KEYS, EXACT_KEYS, POWR_KEYS, camera, compare_exact, frame_inputs, rel_l2
 
 pytestmark = pytest.mark.gpu
 
 CONFIGS = list(REF_CONFIGS)
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+def frame(name, f):
+    """Frame f of the synthetic sequence, in scenes_np.frame's form."""
+    rc = REF_CONFIGS[name]
+    vp, jit = camera(rc, f)
+    return dict(frame_inputs(rc, f), prev_vp=vp, jitter=jit)
 
 
-def bmfr_cfg(rc, library_powr=0) -> bmfr_amd.BmfrConfig:
-    return bmfr_amd.BmfrConfig(image_width=rc.width, image_height=rc.height, not_scaled=rc.not_scaled,
-                               scaled=rc.scaled, use_half_precision_in_tmp_data=rc.half_tmp,
-                               position_limit_squared=rc.position_limit_squared,
-                               normal_limit_squared=rc.normal_limit_squared, library_powr=library_powr)
-
-
-_cache = {}
-
-
-def ref_frames(name, mode="strict"):
-    key = (name, mode)
-    if key not in _cache:
-        rc = REF_CONFIGS[name]
-        if not ref_run.available(name, mode):
-            pytest.skip(f"reference build {name}_{mode} missing (oracle/build_ref.py)")
-        _cache[key] = run_loop(ref_run.RefLoop(rc, mode), rc, rc.frames, to_device=_dev,
-                               sync=torch.cuda.synchronize)
-    return _cache[key]
-
-
-def stage_frames(name, library_powr=0):
-    key = (name, "stages", library_powr)
-    if key not in _cache:
-        rc = REF_CONFIGS[name]
-        _cache[key] = run_loop(bmfr_amd.StagePipeline(bmfr_cfg(rc, library_powr)), rc, rc.frames, to_device=_dev,
-                               sync=torch.cuda.synchronize)
-    return _cache[key]
-
-
-def oracle_frames(name):
-    key = (name, "oracle")
-    if key not in _cache:
-        rc = REF_CONFIGS[name]
-        cfg = pyoracle.make_cfg(rc.width, rc.height, rc.not_scaled, rc.scaled, rc.half_tmp)
-        _cache[key] = run_loop(pyoracle.OracleLoop(cfg), rc, rc.frames)
-    return _cache[key]
+SUITE = Suite(frame, REF_CONFIGS.get, missing_ref=pytest.skip)
+ref_frames, stage_frames, oracle_frames = SUITE.ref_frames, SUITE.stage_frames, SUITE.oracle_frames
 
 
 @pytest.mark.parametrize("name", CONFIGS)
@@ -107,23 +73,14 @@ def test_stage_kernels_match_oracle_bitwise(name, gpu):
 def test_fused_frame_matches_stages_bitwise(name, library_powr, gpu):
     rc = REF_CONFIGS[name]
     st = stage_frames(name, library_powr)
-    den = bmfr_amd.Denoiser(bmfr_cfg(rc, library_powr))
+    den = bmfr_amd.Denoiser(bmfr_cfg(rc, library_powr=library_powr))
     n = rc.width * rc.height
     for f in range(rc.frames):
-        from seq_util import camera, frame_inputs
-        fr = {k: _dev(v) for k, v in frame_inputs(rc, f).items()}
+        fr = {k: to_device(v) for k, v in frame_inputs(rc, f).items()}
         vp, jit = camera(rc, f)
         den.process_frame(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"], vp, jit, f)
-        got = {
-            "result": den.copy_output(torch.empty(3 * n, device="cuda")),
-            "noisy": den.copy_state("noisy_accumulated", torch.empty(3 * n, device="cuda")),
-            "spp": den.copy_state("spp", torch.empty(n, dtype=torch.uint8, device="cuda")),
-            "acc": den.copy_state("filtered_accumulated", torch.empty(3 * n, device="cuda")),
-            "prev_pixel": den.copy_state("prev_frame_pixel", torch.empty(2 * n, device="cuda")),
-        }
-        torch.cuda.synchronize()
-        for k, v in got.items():
-            a, b = v.cpu().numpy(), st[f][k]
+        for k, a in fused_state(den, n).items():
+            b = st[f][k]
             assert a.tobytes() == b.tobytes(), (name, f, k, rel_l2(a, b) if a.dtype == np.float32 else
                                                 int((a != b).sum()))
 

@@ -15,14 +15,12 @@ import bmfr_amd
 from bmfr_amd.tiling import TileGrid
 import prepare_np as pn
 from motion_util import T, quantise, scene_frame, translated
+from parity_harness import STATE, assert_same_array, state_snapshot
+from seq_util import GARBAGE_JITTER, NAN_VP
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-NAN_VP = [float("nan")] * 16
-GARBAGE_JITTER = [float("nan"), 1e30]
-STATE = (("noisy_accumulated", 3, torch.float32), ("spp", 1, torch.uint8), ("filtered_accumulated", 3, torch.float32),
-         ("result", 3, torch.float32), ("prev_frame_pixel", 2, torch.float32))
 
 # name -> make_gbuffer keywords.  Together: every listed format of every plane.
 GBUFFERS = {
@@ -65,26 +63,6 @@ def _synth(W, H, f):
     return fr, vp, jit
 
 
-def _same(got: np.ndarray, want: np.ndarray, what, nan_aware: bool = False):
-    """Byte for byte; nan_aware (inputs that hold NaN only): NaN where the
-    restatement has NaN, whatever its payload, and bytes elsewhere."""
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if nan_aware:
-        nan = np.isnan(want)
-        assert (np.isnan(got) == nan).all(), (what, "NaN positions differ")
-        got, want = np.where(nan, 0, got).astype(got.dtype), np.where(nan, 0, want).astype(want.dtype)
-    a, b = got.view(np.uint8), want.view(np.uint8)
-    bad = np.flatnonzero(a != b)
-    assert bad.size == 0, (what, f"{bad.size} of {a.size} bytes differ, first at byte {int(bad[0])}: "
-                                 f"{got.reshape(-1)[bad[0] // got.itemsize]!r} != {want.reshape(-1)[bad[0] // got.itemsize]!r}")
-
-
-def _state(den, names=STATE) -> dict:
-    n = den.sizes.region_width * den.sizes.region_height
-    return {name: den.copy_state(name, torch.empty(n * ch, dtype=dt, device="cuda")).cpu().numpy()
-            for name, ch, dt in names}
-
-
 # ------------------------------------------------------------------ test 1 --
 # 128 x 80: whole groups only; 101 x 75 = 7575 pixels: 3 (float3) / 7 (half3) pixels past the last group
 @pytest.mark.parametrize("W,H", [(128, 80), (101, 75)])
@@ -102,7 +80,7 @@ def test_kernel_equals_restatement(name, half, W, H, gpu):
     assert set(got) == set(want)
     nan_in = bool(GBUFFERS[name].get("with_nan"))
     for k in pn.OUTPUTS:
-        _same(_host(got[k]), want[k], (name, k), nan_aware=nan_in and k == "albedo")
+        assert_same_array(_host(got[k]), want[k], (name, k), nan_aware=nan_in and k == "albedo")
     if nan_in:
         assert np.isnan(want["albedo"].astype(F32)).any() and np.isfinite(want["noisy"].astype(F32)).all()
 
@@ -135,7 +113,7 @@ def test_planes_off_16_byte_alignment(half, gpu):
     den.prepare(gd, jit, out=out)
     torch.cuda.synchronize()
     for k in outputs:
-        _same(_host(out[k]), want[k], k)
+        assert_same_array(_host(out[k]), want[k], k)
 
 
 # ------------------------------------------------------------------ test 2 --
@@ -151,7 +129,7 @@ def test_tiled_regions_match_untiled(gpu):
     torch.cuda.synchronize()
     want = pn.prepare(g, jit, full, W, H, False)
     for k in pn.OUTPUTS:
-        _same(_host(whole[k]), want[k], ("untiled", k))
+        assert_same_array(_host(whole[k]), want[k], ("untiled", k))
     grid = TileGrid(W, H, 2, 1, halo=halo)
     per_pixel = {k: np.asarray(v).size // (W * H) for k, v in g.items() if k in pn.PLANE_KEYS and k != "object_transforms"}
     for r in range(grid.ranks):
@@ -162,7 +140,7 @@ def test_tiled_regions_match_untiled(gpu):
         got = den.prepare(_dev(gt), jit)
         torch.cuda.synchronize()
         for k in pn.OUTPUTS:
-            _same(_host(got[k]), pn.region_of(_host(whole[k]), W, H, region), (r, k))
+            assert_same_array(_host(got[k]), pn.region_of(_host(whole[k]), W, H, region), (r, k))
 
 
 # ------------------------------------------------------------------ test 3 --
@@ -187,7 +165,7 @@ def _moving_world(ids_value: int):
         prev_q, pos_q = pos_q, quantise(fr["positions"])
         X.process_frame(d["noisy"], d["normals"], t(pos_q), d["albedo"], fr["prev_vp"], fr["jitter"], f,
                         prev_positions=t(prev_q) if f else None, prev_normals=X.prev_inputs[0] if f else None)
-        x = _state(X, names)
+        x = state_snapshot(X, names)
         cur = t(translated(pos_q, f))
         moved = None
         if f:
@@ -199,7 +177,7 @@ def _moving_world(ids_value: int):
                         prev_normals=moved["prev_normals_moved"] if f else None,
                         prev_pixel=t(x["prev_frame_pixel"]) if f else None)
         y_prev = (cur, d["normals"])
-        out.append((x, _state(Y, names)))
+        out.append((x, state_snapshot(Y, names)))
     assert X.frame_status() == 0 and Y.frame_status() == 0
     return out
 
@@ -209,7 +187,7 @@ def test_moving_world_through_prepare(gpu):
     gathers in Y equals X's byte for byte, every frame."""
     for f, (x, y) in enumerate(_moving_world(0)):
         for name in x:
-            _same(y[name], x[name], ("moving world", f, name))
+            assert_same_array(y[name], x[name], ("moving world", f, name))
 
 
 def test_moving_world_ids_past_the_table(gpu):
@@ -241,7 +219,7 @@ def test_motion_vectors_against_projection(gpu):
         fr = scene_frame("synth", W, H, f)
         d = {k: torch.from_numpy(np.array(fr[k])).cuda() for k in ("noisy", "normals", "positions", "albedo")}
         A.process_frame(d["noisy"], d["normals"], d["positions"], d["albedo"], fr["prev_vp"], fr["jitter"], f)
-        a = _state(A, (STATE[1], STATE[4]))
+        a = state_snapshot(A, (STATE[1], STATE[4]))
         plane = a["prev_frame_pixel"].reshape(n, 2).astype(np.float64)
         with np.errstate(all="ignore"):
             mv = np.stack([xs - plane[:, 0], ys - plane[:, 1]], axis=-1).astype(F32)
@@ -254,7 +232,7 @@ def test_motion_vectors_against_projection(gpu):
         worst_px = max(worst_px, np.abs(pp - plane)[inside].max())
         B.process_frame(d["noisy"], d["normals"], d["positions"], d["albedo"], NAN_VP, GARBAGE_JITTER, f,
                         prev_pixel=got["prev_pixel"] if f else None)
-        share = (_state(B, (STATE[1],))["spp"] != a["spp"]).mean()
+        share = (state_snapshot(B, (STATE[1],))["spp"] != a["spp"]).mean()
         worst_share = max(worst_share, share)
     print(f"prepared prev_pixel vs projection: max {worst_px:.2e} px inside the image; "
           f"spp differs on at most {100 * worst_share:.3f} % of pixels per frame")
@@ -291,7 +269,7 @@ def test_process_gbuffer_equals_process_frame(half, gpu):
                         prev_positions=w["prev_positions_moved"] if f else None,
                         prev_pixel=w["prev_pixel"] if f else None)
         last = want
-        a, b = _state(A), _state(B)
+        a, b = state_snapshot(A), state_snapshot(B)
         for name in b:
-            _same(a[name], b[name], (f, name))
+            assert_same_array(a[name], b[name], (f, name))
     assert A.frame_status() == 0 and B.frame_status() == 0

@@ -14,20 +14,11 @@ import torch
 import bmfr_amd
 from bmfr_amd import _lib
 from bmfr_amd.tiling import LoopbackTransport, TileGrid
+from motion_util import REACH_SIZE, shifted
 
 pytestmark = pytest.mark.gpu
 
-W, H, HALO = 320, 256, 40
-
-
-def shifted(vp, dx: float, width: int):
-    """The column-major VP with clip x += (2 dx / width) w: every reprojection
-    lands dx pixels further right (bmfr.cl:343-355)."""
-    k = 2.0 * dx / width
-    m = list(vp)
-    for c in range(4):  # row 0 += k * row 3
-        m[4 * c] += k * m[4 * c + 3]
-    return m
+W, H, HALO = REACH_SIZE
 
 
 def run(dx: float, frames: int = 3, split: bool = True):

@@ -27,7 +27,6 @@ when that file has the configuration."""
 from __future__ import annotations
 
 import dataclasses
-import hashlib
 import json
 import os
 
@@ -36,20 +35,15 @@ import torch
 
 import bmfr_amd
 import ref_run
+from fullsize_util import CASES, DIGESTS, cameras, frame_planes, hip_cfg, sha
+from parity_harness import assert_same, fused_state, rel_l2
 from ref_configs import FULL_REF_CONFIGS
+from seq_util import FUSED_KEYS
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIGESTS = os.path.join(HERE, "golden", "fullsize_digests.json")
 STAGE_KEYS = ("tmp_noisy", "tmp_fit", "weights", "mins_maxs", "filtered", "acc", "tone", "result", "spp",
               "accept", "prev_pixel", "noisy")
-# (test id, reference build, half input planes)
-CASES = [("f1920x1080_h13", "f1920x1080_h13", 0), ("f3840x2160_h13", "f3840x2160_h13", 0),
-         ("f3840x2160_f13", "f3840x2160_f13", 0), ("f3840x2160_h16", "f3840x2160_h16", 0),
-         ("f3840x2160_h16_in16", "f3840x2160_h16", 1), ("f7680x4320_h13", "f7680x4320_h13", 0),
-         ("f1280x720_h13", "f1280x720_h13", 0), ("f1920x1080_h13_60f", "f1920x1080_h13", 0),
-         ("f3840x2160_h13_60f", "f3840x2160_h13", 0)]
 # BASELINE configs 2 and 3 are 60-frame 1080p / 4K sequences: the same builds,
 # all 60 frames (3.75 cycles of the 16 block-grid offsets, spp growing to 60);
 # the first 17 frames' digests are the 17-frame cases'
@@ -61,57 +55,6 @@ FRAMES = {"f1920x1080_h13_60f": 60, "f3840x2160_h13_60f": 60}
 # weights -- and the history blend.  Measured worst: 4.2e-7 (8 ulp of the
 # output value), rel-L2 6.5e-8 (4K, B = 16, frame 12).
 BENCH_REL_L2, BENCH_ABS = 1e-6, 1e-6
-
-
-def bits(t: torch.Tensor) -> torch.Tensor:
-    """Raw bits of a float tensor (NaN-safe bitwise comparison)."""
-    t = t.reshape(-1)
-    if t.dtype == torch.float32:
-        return t.view(torch.int32)
-    if t.dtype == torch.float16:
-        return t.view(torch.int16)
-    return t
-
-
-def assert_same(a: torch.Tensor, b: torch.Tensor, what: str) -> None:
-    a, b = bits(a), bits(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if not torch.equal(a, b):
-        bad = torch.nonzero(a != b).reshape(-1)
-        raise AssertionError(f"{what}: {bad.numel()} of {a.numel()} differ, first at {bad[:5].tolist()}")
-
-
-def rel_l2(a: torch.Tensor, b: torch.Tensor) -> float:
-    a, b = a.double().reshape(-1), b.double().reshape(-1)
-    return float(torch.linalg.norm(a - b) / torch.linalg.norm(b))
-
-
-def sha(t: torch.Tensor) -> str:
-    return hashlib.sha256(bits(t).cpu().numpy().tobytes()).hexdigest()
-
-
-def frame_planes(rc, f: int, half: int):
-    """The synthetic frame f (GPU renderer); with half, rounded to half3 --
-    what the half-input path reads -- and the reference gets those values widened."""
-    fr = bmfr_amd.synth_frame_device(rc.width, rc.height, f, seed=rc.seed)
-    if half:
-        h = {k: fr[k].half() for k in ("noisy", "normals", "positions", "albedo")}
-        return h, {k: v.float() for k, v in h.items()}
-    return fr, fr
-
-
-def cameras(rc, f: int):
-    vp, _ = bmfr_amd.synth_camera(rc.width, rc.height, max(f - 1, 0))
-    _, jit = bmfr_amd.synth_camera(rc.width, rc.height, f)
-    return vp, jit
-
-
-def hip_cfg(rc, half_in: int, library_powr: int = 1) -> bmfr_amd.BmfrConfig:
-    return bmfr_amd.BmfrConfig(image_width=rc.width, image_height=rc.height, not_scaled=rc.not_scaled,
-                               scaled=rc.scaled, use_half_precision_in_tmp_data=rc.half_tmp,
-                               position_limit_squared=rc.position_limit_squared,
-                               normal_limit_squared=rc.normal_limit_squared, library_powr=library_powr,
-                               input_half=half_in)
 
 
 def ulps(a: torch.Tensor, b: torch.Tensor) -> int:
@@ -164,20 +107,13 @@ def test_fullsize_matches_reference_kernels(case, build, half_in, gpu, parity_lo
                 assert_same(srec[k][:rec[k].numel()], rec[k], f"{case} frame {f} stages {k}")
             del srec
         den.process_frame(planes["noisy"], planes["normals"], planes["positions"], planes["albedo"], vp, jit, f)
-        fused = {
-            "result": den.copy_output(torch.empty(3 * n, device="cuda")),
-            "acc": den.copy_state("filtered_accumulated", torch.empty(3 * n, device="cuda")),
-            "noisy": den.copy_state("noisy_accumulated", torch.empty(3 * n, device="cuda")),
-            "spp": den.copy_state("spp", torch.empty(n, dtype=torch.uint8, device="cuda")),
-            "prev_pixel": den.copy_state("prev_frame_pixel", torch.empty(2 * n, device="cuda")),
-        }
+        fused = fused_state(den, n, host=False)
         for k, v in fused.items():
             assert_same(v, rec[k], f"{case} frame {f} fused {k}")
         bench.process_frame(planes["noisy"], planes["normals"], planes["positions"], planes["albedo"], vp, jit, f)
         for k in ("acc", "noisy", "spp", "prev_pixel"):
-            name = {"acc": "filtered_accumulated", "noisy": "noisy_accumulated", "prev_pixel": "prev_frame_pixel"}
             t = torch.empty_like(fused[k])
-            assert_same(bench.copy_state(name.get(k, k), t), rec[k], f"{case} frame {f} bench-config {k}")
+            assert_same(bench.copy_state(FUSED_KEYS[k], t), rec[k], f"{case} frame {f} bench-config {k}")
         out = bench.copy_output(torch.empty(3 * n, device="cuda"))
         b_rel = max(b_rel, rel_l2(out, rec["result"]))
         b_abs = max(b_abs, float((out.double() - rec["result"].double()).abs().max()))

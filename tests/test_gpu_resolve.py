@@ -19,7 +19,7 @@ from bmfr_amd import _lib
 from bmfr_amd.pipeline import hip_memcpy_d2d
 from bmfr_amd.tiling import TileGrid, region_slice, resolve_tiled
 import resolve_np as rn
-from test_gpu_prepare import _same
+from parity_harness import assert_same_array
 
 pytestmark = pytest.mark.gpu
 
@@ -123,13 +123,13 @@ def _compare(got: np.ndarray, want: np.ndarray, fmt, off, what, nan_in: bool):
     buffer viewed as elements from the surface's first byte."""
     dt = rn.FLOAT_DTYPE.get(fmt)
     if dt is None or not nan_in:
-        return _same(got, want, what)
+        return assert_same_array(got, want, what)
     es = np.dtype(dt).itemsize
     a = off % es
     b = a + (got.size - a) // es * es
-    _same(got[:a], want[:a], (what, "front"))
-    _same(got[b:], want[b:], (what, "back"))
-    _same(got[a:b].view(dt), want[a:b].view(dt), what, nan_aware=True)
+    assert_same_array(got[:a], want[:a], (what, "front"))
+    assert_same_array(got[b:], want[b:], (what, "back"))
+    assert_same_array(got[a:b].view(dt), want[a:b].view(dt), what, nan_aware=True)
 
 
 LAYOUTS = list(itertools.product((0, 1), (0, 1), (0, 1)))   # padded pitch, data off a 16-byte boundary, larger surface
@@ -268,7 +268,7 @@ def test_output_f32x3_equals_copy_output(gpu):
         den.resolve(dst)
         want = den.copy_output(torch.empty(W * H * 3, device="cuda"))
         torch.cuda.synchronize()
-        _same(dst.cpu().numpy().reshape(-1), want.cpu().numpy(), ("frame", f))
+        assert_same_array(dst.cpu().numpy().reshape(-1), want.cpu().numpy(), ("frame", f))
     assert den.frame_status() == 0
 
 
@@ -286,7 +286,7 @@ def test_errors_with_a_context_write_nothing(gpu):
             fn()
         assert e.value.status == 1
         for q in surfaces:
-            _same(q.host(), q.expected(), "sentinel")
+            assert_same_array(q.host(), q.expected(), "sentinel")
 
     refused(lambda: den.resolve(s.tensor))                                 # before the first frame
     frames = []
@@ -308,7 +308,7 @@ def test_errors_with_a_context_write_nothing(gpu):
     src, _, surf = den.resolve_args(s.tensor, source="hdr", albedo=albedo)
     st = lib.bmfr_resolve_output(den.handle, None, src, None, C.byref(surf))   # and the library: NULL albedo for HDR
     assert st == 1
-    _same(s.host(), s.expected(), "sentinel")
+    assert_same_array(s.host(), s.expected(), "sentinel")
     den.resolve(s.tensor)                                                  # the same surface is fine once all is in order
     assert (s.host() != rn.SENTINEL).any()
     assert den.frame_status() == 0

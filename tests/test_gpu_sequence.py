@@ -7,19 +7,15 @@ for bit as bmfr_process_frame does, frame by frame -- across chunk
 boundaries and mixed with per-frame calls."""
 from __future__ import annotations
 
-import numpy as np
 import pytest
 import torch
 
 import bmfr_amd
+from parity_harness import same_bits
 
 pytestmark = pytest.mark.gpu
 
 FRAMES = 9
-
-
-def _bits(t: torch.Tensor) -> np.ndarray:
-    return t.cpu().numpy().view(np.uint32)
 
 
 def _frames(W, H, half):
@@ -54,7 +50,7 @@ def test_sequence_matches_per_frame(W, H, kw, streams, gpu, monkeypatch):
     want = []
     for f, (fr, (vp, jit)) in enumerate(seq):
         ref.process_frame(fr["noisy"], fr["normals"], fr["positions"], fr["albedo"], vp, jit, f)
-        want.append(_bits(ref.copy_output(torch.empty(n, device="cuda"))))
+        want.append(ref.copy_output(torch.empty(n, device="cuda")))
     den = bmfr_amd.Denoiser(cfg)
     outs = [torch.full((n,), float("nan"), device="cuda") for _ in range(FRAMES)]
     # chunks [0, 4), then one per-frame call, then [5, 9)
@@ -65,9 +61,9 @@ def test_sequence_matches_per_frame(W, H, kw, streams, gpu, monkeypatch):
     den.process_sequence([s[0] for s in seq[5:]], [s[1] for s in seq[5:]], 5, outputs=outs[5:])
     torch.cuda.synchronize()
     for f in range(FRAMES):
-        assert np.array_equal(_bits(outs[f]), want[f]), f"frame {f}"
-    assert np.array_equal(_bits(den.copy_output(torch.empty(n, device="cuda"))), want[-1])
+        assert same_bits(outs[f], want[f]), f"frame {f}"
+    assert same_bits(den.copy_output(torch.empty(n, device="cuda")), want[-1])
     for name in ("noisy_accumulated", "filtered_accumulated"):
         a = den.copy_state(name, torch.empty(n, device="cuda"))
         b = ref.copy_state(name, torch.empty(n, device="cuda"))
-        assert np.array_equal(_bits(a), _bits(b)), name
+        assert same_bits(a, b), name

@@ -39,23 +39,23 @@ import torch
 
 import aux_np
 import bmfr_amd
-import ref_run
 import shape_util
 from bmfr_amd import _lib
 from bmfr_amd.pipeline import _Context, hip_memcpy_d2d
+from parity_harness import Suite, to_device
 from ref_configs import SHAPE_REF_CONFIGS
-from seq_util import ALL_KEYS, EXACT_KEYS, POWR_KEYS, compare_exact, to_np
-from shape_util import NAMES, PLANES
+from seq_util import ALL_KEYS, EXACT_KEYS, FUSED_KEYS, PLANES, POWR_KEYS, compare_exact
+from shape_util import NAMES
 
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED = 2
-# record key -> bmfr_state plane (the fused kernel keeps the accept bits in registers)
-FUSED_KEYS = {"result": "result", "noisy": "noisy_accumulated", "acc": "filtered_accumulated", "spp": "spp",
-              "prev_pixel": "prev_frame_pixel"}
 SPLIT_NAME = "g_n3s5_h"  # the split / sequence check: an NS = 3 shape
+KEYS = tuple(FUSED_KEYS)
 
-_cache = {}
+# a case is a configuration name; a missing reference build skips
+SUITE = Suite(shape_util.frame, SHAPE_REF_CONFIGS.get, missing_ref=pytest.skip)
+ref_frames, stage_frames = SUITE.ref_frames, SUITE.stage_frames
 
 
 @pytest.fixture(scope="module", params=NAMES)
@@ -63,102 +63,17 @@ def name(request):
     """Module scope: pytest then runs a configuration's tests together, and
     its records (each pipeline run once) are dropped when it is done."""
     yield request.param
-    _cache.clear()
+    SUITE.clear()
     shape_util.forget(request.param)
 
 
-def cached(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()  # a copy: the generator's planes are read-only
-
-
-def bmfr_cfg(rc, library_powr=0, lists=None) -> bmfr_amd.BmfrConfig:
-    not_scaled, scaled = lists or (rc.not_scaled, rc.scaled)
-    return bmfr_amd.BmfrConfig(image_width=rc.width, image_height=rc.height, not_scaled=tuple(not_scaled),
-                               scaled=tuple(scaled), use_half_precision_in_tmp_data=rc.half_tmp,
-                               library_powr=library_powr, **rc.knobs())
-
-
-def ref_frames(name):
-    if not ref_run.available(name, "strict"):
-        pytest.skip(f"reference build {name}_strict missing (oracle/build_ref.py)")
-    rc = SHAPE_REF_CONFIGS[name]
-    return cached((name, "ref"), lambda: shape_util.run_loop(ref_run.RefLoop(rc, "strict"), name, to_device=_dev,
-                                                             sync=torch.cuda.synchronize))
-
-
-def stage_frames(name, library_powr):
-    rc = SHAPE_REF_CONFIGS[name]
-    return cached((name, "stages", library_powr), lambda: shape_util.run_loop(
-        bmfr_amd.StagePipeline(bmfr_cfg(rc, library_powr)), name, to_device=_dev, sync=torch.cuda.synchronize))
-
-
-def fused_state(den, n) -> dict:
-    f32 = lambda m: torch.empty(m, device="cuda")  # noqa: E731
-    out = {"result": den.copy_output(f32(3 * n))}
-    for k, plane in FUSED_KEYS.items():
-        if k != "result":
-            out[k] = den.copy_state(plane, torch.empty(n, dtype=torch.uint8, device="cuda") if k == "spp"
-                                    else f32((2 if k == "prev_pixel" else 3) * n))
-    torch.cuda.synchronize()
-    return {k: to_np(v).copy() for k, v in out.items()}
-
-
-def device_frames(name, aux_names=()):
-    """Per frame: dict of the planes on the device (aux: the planes of
-    aux_names, None where not named), previous camera, jitter."""
-    rc = SHAPE_REF_CONFIGS[name]
-    out = []
-    for f in range(rc.frames):
-        fr = shape_util.frame(name, f)
-        d = {k: _dev(fr[k]) for k in PLANES}
-        d["aux"] = [None if p is None else _dev(p) for p in
-                    aux_np.aux_planes(aux_names, fr["normals"], fr["positions"], fr["albedo"], rc.width, rc.height)]
-        out.append((d, fr["prev_vp"], fr["jitter"]))
-    return out
-
-
-def fused_frames(name, library_powr, aux=False, mode="frame"):
+def fused_frames(name, library_powr, aux=False, mode="frame", keep=False):
     """The Denoiser over the configuration's frames -> per-frame state.  aux:
     the list of shape_util.aux_case, with its planes.  mode: "frame", "split"
     (_interior + _border) or "sequence" (one process_sequence call; ->
-    (per-frame outputs, last state))."""
-    rc = SHAPE_REF_CONFIGS[name]
-    n = rc.width * rc.height
-    not_scaled, scaled, aux_names = shape_util.aux_case(name) if aux else (rc.not_scaled, rc.scaled, ())
-    den = bmfr_amd.Denoiser(bmfr_cfg(rc, library_powr, (not_scaled, scaled)))
-    frames = device_frames(name, aux_names)
-    if mode == "sequence":
-        outs = [torch.empty(3 * n, device="cuda") for _ in frames]
-        den.process_sequence([d for d, _, _ in frames], [(vp, jit) for _, vp, jit in frames], 0, outputs=outs)
-        torch.cuda.synchronize()
-        assert den.frame_status() == 0
-        return [{"result": to_np(o).copy()} for o in outs], fused_state(den, n)
-    out = []
-    for f, (d, vp, jit) in enumerate(frames):
-        args = (d["noisy"], d["normals"], d["positions"], d["albedo"], vp, jit, f)
-        if mode == "split":
-            den.process_frame_interior(*args, aux=d["aux"])
-            den.process_frame_border(*args, aux=d["aux"])
-        else:
-            den.process_frame(*args, aux=d["aux"])
-        out.append(fused_state(den, n))
-    assert den.frame_status() == 0
-    return out
-
-
-def compare_bytes(got, want, where, keys=tuple(FUSED_KEYS)):
-    for f, (g, w) in enumerate(zip(got, want)):
-        for k in keys:
-            a, b = np.frombuffer(g[k].tobytes(), np.uint8), np.frombuffer(w[k].tobytes(), np.uint8)
-            assert a.size == b.size, (where, f, k, a.size, b.size)
-            bad = np.flatnonzero(a != b)
-            assert bad.size == 0, f"{where} frame {f} {k}: {bad.size} of {a.size} bytes differ, first at byte {bad[0]}"
+    (per-frame outputs, last state)).  keep: run once per configuration."""
+    run = SUITE.kept_fused_frames if keep else SUITE.fused_frames
+    return run(name, aux=aux, mode=mode, library_powr=library_powr)
 
 
 # ------------------------------------------------------ the sweep, per name ----
@@ -186,8 +101,8 @@ def test_stage_kernels_match_oracle_bitwise(name, gpu):
 @pytest.mark.parametrize("library_powr", [0, 1])
 def test_fused_frame_matches_stages_bitwise(name, library_powr, gpu):
     """k_fused_block<NS, FS, HALF>."""
-    fused = cached((name, "fused", library_powr), lambda: fused_frames(name, library_powr))
-    compare_bytes(fused, stage_frames(name, library_powr), f"fused vs stages[{name} powr {library_powr}]")
+    fused = fused_frames(name, library_powr, keep=True)
+    compare_exact(fused, stage_frames(name, library_powr), KEYS, f"fused vs stages[{name} powr {library_powr}]")
 
 
 @pytest.mark.parametrize("library_powr", [0, 1])
@@ -203,8 +118,8 @@ def test_aux_kernel_equals_named(name, library_powr, gpu):
     for k, nm in enumerate(aux_names):  # plane k holds the code it replaced
         if nm is not None:
             assert (rc.not_scaled + rc.scaled)[codes.index(aux_np.AUX0 + k)] == aux_np.CODE_OF[nm]
-    named = cached((name, "fused", library_powr), lambda: fused_frames(name, library_powr))
-    compare_bytes(fused_frames(name, library_powr, aux=True), named, f"aux vs named[{name} powr {library_powr}]")
+    named = fused_frames(name, library_powr, keep=True)
+    compare_exact(fused_frames(name, library_powr, aux=True), named, KEYS, f"aux vs named[{name} powr {library_powr}]")
 
 
 # ------------------------------------------- split and sequence at NS = 3 ----
@@ -212,7 +127,7 @@ def test_aux_kernel_equals_named(name, library_powr, gpu):
 def test_interior_border_equals_frame(aux, gpu):
     whole = fused_frames(SPLIT_NAME, 0, aux=aux)
     split = fused_frames(SPLIT_NAME, 0, aux=aux, mode="split")
-    compare_bytes(split, whole, "_interior + _border vs process_frame")
+    compare_exact(split, whole, KEYS, "_interior + _border vs process_frame")
 
 
 @pytest.mark.parametrize("schedule", ["fused", "streams"])
@@ -224,8 +139,8 @@ def test_sequence_equals_frames(aux, schedule, gpu, monkeypatch):
         monkeypatch.delenv("BMFR_SEQUENCE", raising=False)
     per_frame = fused_frames(SPLIT_NAME, 0, aux=aux)
     outs, last = fused_frames(SPLIT_NAME, 0, aux=aux, mode="sequence")
-    compare_bytes(outs, per_frame, "process_sequence outputs vs process_frame", keys=("result",))
-    compare_bytes([last], [per_frame[-1]], "process_sequence state vs process_frame")
+    compare_exact(outs, per_frame, ("result",), "process_sequence outputs vs process_frame")
+    compare_exact([last], [per_frame[-1]], KEYS, "process_sequence state vs process_frame")
 
 
 # ------------------------------- feature counts outside the instantiated range ----
@@ -275,7 +190,7 @@ def test_counts_outside_the_instantiated_range_are_unsupported(case, gpu):
         hip_memcpy_d2d(ptr, pattern.data_ptr(), nbytes)
     before = _snapshot(den)
     fr = shape_util.frame("g_n1s0_h", 0)
-    d = {k: _dev(fr[k]) for k in PLANES}
+    d = {k: to_device(fr[k]) for k in PLANES}
     keep = {k: v.clone() for k, v in d.items()}
     names_aux = any(c >= _lib.FEATURE_AUX0 for c in not_scaled + scaled)
     plane = torch.ones(W * H, device="cuda")

@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 import exr_dwa_py
-from test_image_io import DWA_OPTS, _attr, _dwa_image, _img, write_exr_py
+from exr_write_py import DWA_OPTS, _attr, _dwa_image, _img, write_exr_py
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
