@@ -129,7 +129,18 @@ __global__ __launch_bounds__(kTaaNT, kTaaMinWaves) void k_fused_taa(Params P, Ta
     __shared__ double2 sRP[kPowrRPNum];
     // Output tile of this launch (the whole image, or a multi-GPU tile whose
     // one-pixel halo lies inside the buffer region).
-    const int gi = xcd_swizzle(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    // Against K1's order: the last tile row first, every XCD's band bottom-up
+    // (G - 1 - the swizzled index: still a bijection on [0, G)).  K1, launched
+    // just before, wrote the accumulated colour and reprojected positions top
+    // to bottom; read newest first, part of them is still in the 256 MiB
+    // last-level cache, where the forward order re-read every row a whole
+    // frame's traffic (1.45 GB at 4K) after it was written.  K2 at 4K -2.4 /
+    // -2.7 % in every one of 10 interleaved rounds (0.0946 -> 0.0923, 0.0979
+    // -> 0.0953 ms, two boxes; K1 is the same code, so the frame gains what K2
+    // does, 0.7-1 %), profiles/r07_l3_handoff.txt; the one-launch frame's
+    // tiles keep K1's order: they wait on K1 blocks in dispatch order.
+    const int G = gridDim.x * gridDim.y;
+    const int gi = G - 1 - xcd_swizzle(blockIdx.y * gridDim.x + blockIdx.x, G);
     const int bxi = gi % gridDim.x, byi = gi / gridDim.x;
     forward_reach(T, blockIdx.x == 0 && blockIdx.y == 0);
     taa_tile<IN, kTaaH, false>(P, T, P.tx0 + bxi * kTaaW, P.ty0 + byi * kTaaH, Y, sE, sRP);
