@@ -124,6 +124,22 @@ class Surface(C.Structure):
     ]
 
 
+# bmfr_upsample_source
+UPSAMPLE_HDR, UPSAMPLE_TONEMAPPED = 0, 1
+
+
+class UpsampleGuides(C.Structure):
+    """bmfr_upsample_guides: the display-resolution G-buffer of bmfr_upsample_output (include/bmfr.h)."""
+    _fields_ = [
+        ("width", C.c_int), ("height", C.c_int),
+        ("albedo", C.c_void_p), ("albedo_format", C.c_int),
+        ("normals", C.c_void_p), ("normal_format", C.c_int),
+        ("positions", C.c_void_p), ("depth", C.c_void_p),
+        ("inv_view_proj", C.c_float * 16), ("pixel_offset", C.c_float * 2),
+        ("plane_limit_squared", C.c_float), ("normal_limit_squared", C.c_float),
+    ]
+
+
 class FireflyParams(C.Structure):
     """bmfr_firefly_params: the rule of bmfr_suppress_fireflies (include/bmfr.h)."""
     _fields_ = [("threshold", C.c_float), ("radius", C.c_int), ("floor", C.c_float), ("replace_nonfinite", C.c_int)]
@@ -163,6 +179,8 @@ SIGNATURES = {
     "bmfr_prepare_frame": (_I, [_P, _P, C.POINTER(GBuffer), C.POINTER(Prepared), _F2]),
     "bmfr_surface_default": (None, [C.POINTER(Surface)]),
     "bmfr_resolve_output": (_I, [_P, _P, _I, _P, C.POINTER(Surface)]),
+    "bmfr_upsample_guides_default": (None, [C.POINTER(UpsampleGuides), C.POINTER(Config)]),
+    "bmfr_upsample_output": (_I, [_P, _P, _I, _P, _P, C.POINTER(UpsampleGuides), C.POINTER(Surface), _P]),
     "bmfr_firefly_default": (None, [C.POINTER(FireflyParams)]),
     "bmfr_suppress_fireflies": (_I, [_P, _P, _P, _P, C.POINTER(FireflyParams), _P]),
     "bmfr_halo_copy": (_I, [_P, _P, C.POINTER(C.c_int), _I, _P, _I, C.POINTER(C.c_size_t)]),

@@ -18,6 +18,7 @@
 #include "bmfr_launch.h"
 #include "bmfr_prepare.h"
 #include "bmfr_resolve.h"
+#include "bmfr_upsample.h"
 
 using bmfr::Params;
 
@@ -1077,8 +1078,8 @@ void bmfr_surface_default(bmfr_surface* s) {
 
 namespace {
 
-// dst, source and albedo alone (no context, no device).
-bmfr_status check_resolve_args(int source, const void* albedo, const bmfr_surface* d) {
+// dst alone (no context, no device).
+bmfr_status check_surface(const bmfr_surface* d) {
     if (!d || !d->data || d->width <= 0 || d->height <= 0) return BMFR_ERROR_INVALID_ARGUMENT;
     size_t bpp, align;
     switch (d->format) {
@@ -1092,6 +1093,13 @@ bmfr_status check_resolve_args(int source, const void* albedo, const bmfr_surfac
     if (d->pitch < (size_t)d->width * bpp || d->pitch % align != 0 || reinterpret_cast<uintptr_t>(d->data) % align != 0 ||
         d->pitch > (size_t)1 << 31)  // row * pitch stays inside 64 bits
         return BMFR_ERROR_INVALID_ARGUMENT;
+    return BMFR_OK;
+}
+
+// dst, source and albedo alone (no context, no device).
+bmfr_status check_resolve_args(int source, const void* albedo, const bmfr_surface* d) {
+    const bmfr_status st = check_surface(d);
+    if (st != BMFR_OK) return st;
     if (source != BMFR_RESOLVE_OUTPUT && source != BMFR_RESOLVE_HDR) return BMFR_ERROR_INVALID_ARGUMENT;
     if (source == BMFR_RESOLVE_HDR && !albedo) return BMFR_ERROR_INVALID_ARGUMENT;
     return BMFR_OK;
@@ -1131,6 +1139,98 @@ bmfr_status bmfr_resolve_output(bmfr_ctx* c, void* stream, int source, const voi
     a.dy_step = d->flip_y ? -1 : 1;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_resolve(a, as_stream(stream)));
+}
+
+// ------------------------------------------------- guided upsampling ----
+void bmfr_upsample_guides_default(bmfr_upsample_guides* g, const bmfr_config* cfg) {
+    if (!g) return;
+    std::memset(g, 0, sizeof *g);
+    bmfr_config d;
+    if (!cfg) bmfr_config_default(&d, BMFR_BLOCK_EDGE_LENGTH, BMFR_BLOCK_EDGE_LENGTH);
+    g->plane_limit_squared = as_kernel_literal((cfg ? cfg : &d)->position_limit_squared);
+    g->normal_limit_squared = as_kernel_literal((cfg ? cfg : &d)->normal_limit_squared);
+}
+
+namespace {
+
+bool aligned_to(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+// source, the guides, the frame planes and stats alone (no context, no device).
+bmfr_status check_upsample_args(int source, const void* frame_normals, const void* frame_positions,
+                                const bmfr_upsample_guides* g, const uint32_t* stats) {
+    if (source != BMFR_UPSAMPLE_HDR && source != BMFR_UPSAMPLE_TONEMAPPED) return BMFR_ERROR_INVALID_ARGUMENT;
+    if (!g || !g->albedo || g->width <= 0 || g->height <= 0) return BMFR_ERROR_INVALID_ARGUMENT;
+    const bool has_position = g->positions || g->depth;
+    if ((g->normals != nullptr) != has_position) return BMFR_ERROR_INVALID_ARGUMENT;
+    if (g->normals && (!frame_normals || !frame_positions)) return BMFR_ERROR_INVALID_ARGUMENT;
+    for (float limit : {g->plane_limit_squared, g->normal_limit_squared})
+        if (!std::isfinite(limit) || !(limit > 0.0f)) return BMFR_ERROR_INVALID_ARGUMENT;
+    if (!format_listed(g->albedo, g->albedo_format, {BMFR_FORMAT_F32X3, BMFR_FORMAT_F16X4, BMFR_FORMAT_UNORM8X4}) ||
+        !format_listed(g->normals, g->normal_format,
+                       {BMFR_FORMAT_F32X3, BMFR_FORMAT_F16X4, BMFR_FORMAT_OCT_SNORM16X2}))
+        return BMFR_ERROR_UNSUPPORTED;
+    if (!aligned_to(g->albedo, g->albedo_format == BMFR_FORMAT_F16X4 ? 8 : 4) ||
+        !aligned_to(g->normals, g->normal_format == BMFR_FORMAT_F16X4 ? 8 : 4) || !aligned_to(g->positions, 4) ||
+        !aligned_to(g->depth, 4) || !aligned_to(stats, sizeof(uint32_t)))
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    return BMFR_OK;
+}
+
+}  // namespace
+
+bmfr_status bmfr_upsample_output(bmfr_ctx* c, void* stream, int source, const void* frame_normals,
+                                 const void* frame_positions, const bmfr_upsample_guides* g, const bmfr_surface* d,
+                                 uint32_t* stats) {
+    bmfr_status st = check_surface(d);
+    if (st == BMFR_OK) st = check_upsample_args(source, frame_normals, frame_positions, g, stats);
+    if (st != BMFR_OK) return st;
+    if (!c || !c->has_frame || c->pending_frame >= 0) return BMFR_ERROR_INVALID_ARGUMENT;
+    const bmfr_config& cfg = c->cfg;
+    // a tile's taps reach one pixel past it, where filtered_accumulated holds the previous exchange
+    if (is_tiled(&cfg)) return BMFR_ERROR_UNSUPPORTED;
+    const int W = cfg.image_width, H = cfg.image_height, Wd = g->width, Hd = g->height;
+    if (Wd < W || Hd < H || Wd > 4ll * W || Hd > 4ll * H) return BMFR_ERROR_INVALID_ARGUMENT;
+    const bool guided = g->normals != nullptr;
+    const uintptr_t elem = cfg.input_half ? 2 : 4;
+    if (guided && (!aligned_to(frame_normals, elem) || !aligned_to(frame_positions, elem)))
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    // the Wd x Hd frame's rectangle in the surface (64-bit: origins are the caller's)
+    const long long x0 = d->origin_x, y0 = d->origin_y;
+    if (x0 < 0 || y0 < 0 || x0 + Wd > d->width || y0 + Hd > d->height) return BMFR_ERROR_INVALID_ARGUMENT;
+    bmfr::UpsampleArgs a{};
+    a.acc = c->acc[c->cur];
+    a.f_normals = guided ? frame_normals : nullptr;
+    a.f_positions = guided ? frame_positions : nullptr;
+    a.albedo = g->albedo;
+    a.normals = g->normals;
+    a.positions = g->positions;
+    a.depth = g->depth;
+    a.dst = d->data;
+    a.stats = guided ? stats : nullptr;
+    a.pitch = (long long)d->pitch;
+    std::memcpy(a.m, g->inv_view_proj, sizeof a.m);
+    a.jx = g->pixel_offset[0];
+    a.jy1 = 1.0f - g->pixel_offset[1];
+    a.rx = (float)W / (float)Wd;
+    a.ry = (float)H / (float)Hd;
+    a.plane_limit_sq = g->plane_limit_squared;
+    a.normal_limit_sq = g->normal_limit_squared;
+    a.alpha = d->alpha;
+    a.format = d->format;
+    a.albedo_fmt = g->albedo_format;
+    a.normal_fmt = g->normal_format;
+    a.frame_half = cfg.input_half != 0;
+    a.tonemapped = source == BMFR_UPSAMPLE_TONEMAPPED;
+    a.bgr = d->bgr != 0;
+    a.W = W;
+    a.H = H;
+    a.Wd = Wd;
+    a.Hd = Hd;
+    a.dx0 = (int)x0;
+    a.dy0 = (int)(d->flip_y ? y0 + Hd - 1 : y0);  // display row 0 is the rectangle's last row when flipped
+    a.dy_step = d->flip_y ? -1 : 1;
+    DeviceGuard guard(c->device);
+    return hip_status(bmfr::launch_upsample(a, as_stream(stream)));
 }
 
 // ------------------------------------------------- firefly pre-filter ----

@@ -378,17 +378,17 @@ class Denoiser(_Context):
     _PREPARED = ("noisy", "normals", "positions", "albedo", "prev_pixel", "prev_positions_moved",
                  "prev_normals_moved")
 
-    def _check_plane(self, name: str, t, dtypes):
+    def _check_plane(self, name: str, t, dtypes, pixels: int | None = None):
         """A plane handed to the library: a contiguous tensor on this GPU of
         one of `dtypes` (dtype -> (format, elements per pixel)) covering the
-        region.  Runs before the call, which would read a wrong plane out of
-        bounds.  -> the dtype's format."""
+        region (or `pixels` pixels).  Runs before the call, which would read a
+        wrong plane out of bounds.  -> the dtype's format."""
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch tensor, not {type(t).__name__}")
         if t.dtype not in dtypes:
             raise TypeError(f"{name} must be one of {[str(d) for d in dtypes]}, not {t.dtype}")
         fmt, per = dtypes[t.dtype]
-        n = self.sizes.region_width * self.sizes.region_height * per
+        n = (self.sizes.region_width * self.sizes.region_height if pixels is None else pixels) * per
         if t.numel() != n or not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous with {n} elements, not {tuple(t.shape)}")
         if t.device.type != "cuda" or (t.device.index or 0) != self.device:
@@ -605,6 +605,23 @@ class Denoiser(_Context):
         """The checked arguments of bmfr_resolve_output -> (source code, albedo
         pointer, bmfr_surface); a caller that repeats a call keeps them.  Runs
         before the call, which would write a wrong surface out of bounds."""
+        s = self._surface(dst, origin, flip_y, bgr, alpha)
+        if source not in self._RESOLVE_SOURCES:
+            raise ValueError(f"source must be one of {sorted(self._RESOLVE_SOURCES)}, not {source!r}")
+        if source == "hdr":
+            if albedo is None:
+                raise ValueError("source 'hdr' needs the frame's albedo plane")
+            self._check_plane("albedo", albedo, {torch.float16 if self.cfg.input_half else torch.float32: (None, 3)})
+        self._check_surface_device(dst)
+        return self._RESOLVE_SOURCES[source], (_ptr(albedo) if source == "hdr" else None), s
+
+    def _check_surface_device(self, dst) -> None:
+        if dst.device.type != "cuda" or (dst.device.index or 0) != self.device:
+            raise ValueError(f"dst must live on cuda:{self.device}, not {dst.device}")
+
+    def _surface(self, dst, origin, flip_y, bgr, alpha) -> _lib.Surface:
+        """The bmfr_surface of a destination tensor (resolve's docstring); its
+        device is checked apart (_check_surface_device)."""
         if not isinstance(dst, torch.Tensor):
             raise TypeError(f"dst must be a torch tensor, not {type(dst).__name__}")
         channels = dst.shape[2] if dst.dim() == 3 else None
@@ -616,21 +633,13 @@ class Denoiser(_Context):
         if dst.numel() == 0 or tuple(dst.stride()[1:]) != inner or dst.stride(0) < dst.shape[1] * (channels or 1):
             raise ValueError(f"dst must have packed pixels and rows that do not overlap (strides {dst.stride()}); "
                              "only its row stride is free")
-        if source not in self._RESOLVE_SOURCES:
-            raise ValueError(f"source must be one of {sorted(self._RESOLVE_SOURCES)}, not {source!r}")
-        if source == "hdr":
-            if albedo is None:
-                raise ValueError("source 'hdr' needs the frame's albedo plane")
-            self._check_plane("albedo", albedo, {torch.float16 if self.cfg.input_half else torch.float32: (None, 3)})
-        if dst.device.type != "cuda" or (dst.device.index or 0) != self.device:
-            raise ValueError(f"dst must live on cuda:{self.device}, not {dst.device}")
         s = _lib.Surface()
         self.lib.bmfr_surface_default(C.byref(s))
         s.data, s.format, s.pitch = dst.data_ptr(), fmt, dst.stride(0) * dst.element_size()
         s.width, s.height = dst.shape[1], dst.shape[0]
         s.origin_x, s.origin_y = int(origin[0]), int(origin[1])
         s.flip_y, s.bgr, s.alpha = int(bool(flip_y)), int(bool(bgr)), float(alpha)
-        return self._RESOLVE_SOURCES[source], (_ptr(albedo) if source == "hdr" else None), s
+        return s
 
     def resolve(self, dst, source="output", albedo=None, origin=(0, 0), flip_y=False, bgr=False, alpha=1.0,
                 stream=None):
@@ -645,6 +654,88 @@ class Denoiser(_Context):
         pixel (0, 0), negative for a tile-sized surface.  -> dst."""
         src, alb, s = self.resolve_args(dst, source, albedo, origin, flip_y, bgr, alpha)
         check(self.lib.bmfr_resolve_output(self.handle, _stream(stream), src, alb, C.byref(s)), "bmfr_resolve_output")
+        return dst
+
+    # ---- Guided upsampling (include/bmfr.h bmfr_upsample_output) ----
+    _UPSAMPLE_SOURCES = {"hdr": _lib.UPSAMPLE_HDR, "tonemapped": _lib.UPSAMPLE_TONEMAPPED}
+    # guide -> (format field, dtype -> (format, elements per pixel))
+    _GUIDE_PLANES = {
+        "albedo": ("albedo_format", {torch.float32: (_lib.FORMAT_F32X3, 3), torch.float16: (_lib.FORMAT_F16X4, 4),
+                                     torch.uint8: (_lib.FORMAT_UNORM8X4, 4)}),
+        "normals": ("normal_format", {torch.float32: (_lib.FORMAT_F32X3, 3), torch.float16: (_lib.FORMAT_F16X4, 4),
+                                      torch.int16: (_lib.FORMAT_OCT_SNORM16X2, 2)}),
+        "positions": (None, {torch.float32: (None, 3)}),
+        "depth": (None, {torch.float32: (None, 1)}),
+    }
+
+    def upsample_args(self, dst, guides: dict, normals=None, positions=None, source="hdr", origin=(0, 0),
+                      flip_y=False, bgr=False, alpha=1.0, stats=None):
+        """The checked arguments of bmfr_upsample_output -> (source code,
+        bmfr_upsample_guides, bmfr_surface); a caller that repeats a call keeps
+        them.  Runs before the call, which would read a wrong plane or write a
+        wrong surface out of bounds."""
+        s = self._surface(dst, origin, flip_y, bgr, alpha)
+        if source not in self._UPSAMPLE_SOURCES:
+            raise ValueError(f"source must be one of {sorted(self._UPSAMPLE_SOURCES)}, not {source!r}")
+        unknown = set(guides) - {f[0] for f in _lib.UpsampleGuides._fields_ if not f[0].endswith("_format")}
+        if unknown:
+            raise KeyError(f"unknown guide {sorted(unknown)!r}")
+        g = _lib.UpsampleGuides()
+        self.lib.bmfr_upsample_guides_default(C.byref(g), C.byref(self.cfg.to_c()))
+        g.width, g.height = int(guides.get("width", 0)), int(guides.get("height", 0))
+        if g.width <= 0 or g.height <= 0:
+            raise ValueError("guides need the display size: width and height")
+        if guides.get("albedo") is None:
+            raise ValueError("guides need the display-resolution albedo plane")
+        for name, (fmt_field, dtypes) in self._GUIDE_PLANES.items():
+            t = guides.get(name)
+            if t is None:
+                continue
+            fmt = self._check_plane(f"guides[{name!r}]", t, dtypes, pixels=g.width * g.height)
+            setattr(g, name, t.data_ptr())
+            if fmt_field:
+                setattr(g, fmt_field, fmt)
+        if guides.get("inv_view_proj") is not None:
+            g.inv_view_proj[:] = [float(v) for v in guides["inv_view_proj"]]
+        if guides.get("pixel_offset") is not None:
+            g.pixel_offset[:] = [float(v) for v in guides["pixel_offset"]]
+        for name in ("plane_limit_squared", "normal_limit_squared"):
+            if name in guides:
+                setattr(g, name, float(guides[name]))
+        if guides.get("normals") is not None:   # guided: the frame's own planes
+            frame = {torch.float16 if self.cfg.input_half else torch.float32: (None, 3)}
+            for name, t in (("normals", normals), ("positions", positions)):
+                if t is None:
+                    raise ValueError(f"guided upsampling needs the frame's {name} plane")
+                self._check_plane(name, t, frame)
+        if stats is not None:
+            if not isinstance(stats, torch.Tensor) or stats.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) \
+                    or stats.numel() != 1 or not stats.is_contiguous() or stats.device.type != "cuda" \
+                    or (stats.device.index or 0) != self.device:
+                raise ValueError(f"stats must be a contiguous tensor of one 32-bit integer on cuda:{self.device}")
+        self._check_surface_device(dst)
+        return self._UPSAMPLE_SOURCES[source], g, s
+
+    def upsample(self, dst, guides: dict, normals=None, positions=None, source="hdr", origin=(0, 0), flip_y=False,
+                 bgr=False, alpha=1.0, stats=None, stream=None):
+        """bmfr_upsample_output: the last frame's filtered_accumulated stretched
+        to the display resolution of `guides`, taps on another surface than the
+        display pixel left out, times the display-resolution albedo, into the
+        surface `dst` (as resolve takes it) in one kernel launch.  guides: the
+        renderer's display-resolution G-buffer by the names of
+        bmfr_upsample_guides -- width, height, albedo (float32 / float16 =
+        RGBA16F / uint8 = UNORM8X4), and for guided mode normals (float32 /
+        float16 / int16 = octahedral) with positions or depth (with
+        inv_view_proj, 16 floats column-major, and pixel_offset);
+        plane_limit_squared / normal_limit_squared default to the
+        configuration's limits.  normals, positions: the frame's planes as given
+        to process_frame (guided mode).  source: "hdr" (linear) or "tonemapped"
+        (display-referred).  stats: an int32 tensor of one counter, the pixels
+        none of whose taps passed, which the call adds to.  Untiled contexts
+        only.  -> dst."""
+        src, g, s = self.upsample_args(dst, guides, normals, positions, source, origin, flip_y, bgr, alpha, stats)
+        check(self.lib.bmfr_upsample_output(self.handle, _stream(stream), src, _ptr(normals), _ptr(positions),
+                                            C.byref(g), C.byref(s), _ptr(stats)), "bmfr_upsample_output")
         return dst
 
     @property

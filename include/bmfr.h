@@ -735,6 +735,116 @@ void bmfr_surface_default(bmfr_surface *s);   /* zeroes *s; alpha = 1 */
 bmfr_status bmfr_resolve_output(bmfr_ctx *ctx, void *stream, int source,
                                 const void *albedo, const bmfr_surface *dst);
 
+/* ---- Guided upsampling: a frame traced below display resolution ----
+ * (no reference counterpart: the reference denoises and shows one resolution.)
+ *
+ * A renderer that traces at W x H and shows Wd x Hd still rasterises its
+ * G-buffer -- albedo, normals, depth -- at display resolution.  What the
+ * library filters and accumulates, filtered_accumulated, is irradiance with the
+ * texture detail divided out, so it stretches well; the detail is in the
+ * albedo, which the renderer has at full resolution.  bmfr_upsample_output
+ * interpolates the last processed frame's filtered_accumulated to Wd x Hd,
+ * leaving out the taps that lie on another surface than the display pixel,
+ * multiplies by the display-resolution albedo and writes a bmfr_surface, in one
+ * kernel launch on `stream`.  It delivers the denoised, temporally accumulated,
+ * remodulated image; it does NOT run TAA at display resolution:
+ * display-resolution anti-aliasing stays the renderer's.
+ *
+ * Planes.  The guides cover Wd x Hd with row stride Wd, one element per pixel
+ * in the plane's bmfr_format, device memory aligned to the element (4 bytes;
+ * 8 for F16X4).  frame_normals / frame_positions are the frame's planes as
+ * given to bmfr_process_frame: W x H, f32x3, or half3 widened exactly in an
+ * input_half context.  dst is a bmfr_surface as bmfr_resolve_output takes it;
+ * the frame that is placed has size Wd x Hd: display pixel (X, Y) goes to
+ * surface pixel (origin_x + X, origin_y + (flip_y ? Hd - 1 - Y : Y)), and
+ * nothing else of the surface is written.
+ *
+ * Arithmetic: every line is one f32 operation rounded once, associated as
+ * written, never contracted, with division correctly rounded.  For display
+ * pixel (X, Y), W x H the context's frame:
+ *
+ *  1. Footprint.  rx = float(W) / float(Wd), ry = float(H) / float(Hd), once.
+ *       u = (float(X) + 0.5f) * rx - 0.5f;    v = (float(Y) + 0.5f) * ry - 0.5f
+ *       x0 = floorf(u);  fx = u - x0;         y0 = floorf(v);  fy = v - y0
+ *     Taps k = (i, j) in the order 00, 10, 01, 11 at frame pixel
+ *       (clamp(x0 + i, 0, W - 1),  clamp(y0 + j, 0, H - 1))    with weight
+ *       w_k = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy)
+ *  2. Display guides.  A (albedo), N (normal), P (world position) of the
+ *     display pixel come from the guides, decoded exactly as bmfr_prepare_frame
+ *     decodes the same formats -- the octahedral rule included, and for `depth`
+ *     the position-from-depth lines with (x, y) = (X, Y), (W, H) = (Wd, Hd) and
+ *     (jx, jy) = the guides' pixel_offset.
+ *  3. Tap test.  n_k, p_k = frame_normals / frame_positions at the tap.
+ *       dp = p_k - P;    d = (dp.x*N.x + dp.y*N.y) + dp.z*N.z
+ *       dn = n_k - N;    q = (dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z
+ *     The tap is accepted when
+ *       w_k > 0 && d*d < plane_limit_squared && q < normal_limit_squared
+ *     (a NaN compares false).  d is the distance to the display pixel's tangent
+ *     plane, not the Euclidean distance: the test does not depend on the
+ *     pixel footprint.
+ *  4. Accumulate.  e_k = filtered_accumulated at the tap.  sw = the sum, in
+ *     tap order, of w_k over the accepted taps, and sc that of w_k * e_k per
+ *     channel; a sum begins with its first term (a single tap of weight 1
+ *     passes e_k through, the sign of a zero included).
+ *       accepted taps exist and sw > 0:   e = sc / sw
+ *       otherwise the pixel falls back: the same sums over every tap with
+ *       w_k > 0, and stats[0] counts the pixel.
+ *     A tap of weight 0 is never read into a sum: 0 * NaN does not reach e.
+ *  5. Unguided mode: normals NULL, and positions and depth both NULL.  Every
+ *     tap with w_k > 0 is accepted and stats counts nothing.
+ *  6. Source value.  c = A * e per channel.
+ *       BMFR_UPSAMPLE_HDR:         v = c
+ *       BMFR_UPSAMPLE_TONEMAPPED:  v = min(max(powr(max(0, c), 0.454545f), 0), 1)
+ *     with the correctly rounded powr (the function tone_map uses by default,
+ *     equal to the oracle's (float)pow) whatever the context's library_powr.
+ *     v is encoded exactly as bmfr_resolve_output encodes it (bgr, alpha).
+ *
+ * Ordering and state as bmfr_resolve_output: enqueued on `stream`, ordered
+ * after the frame by the caller, valid until the next bmfr_process_frame*.
+ * It reads filtered_accumulated and changes neither the context's state, nor
+ * the frame status, nor what bmfr_frame_status waits for.
+ *
+ * stats (nullable): one uint32_t in device memory, the fallback pixels.  The
+ * call adds to it; the caller zeroes it.
+ *
+ * Known limit: tiled contexts are refused (BMFR_ERROR_UNSUPPORTED).  A tile's
+ * taps reach one pixel past it, and the halo of filtered_accumulated there
+ * holds the previous exchange, not this frame; exchanging a one-pixel ring
+ * after the frame is a follow-up.
+ *
+ * Errors.  dst is checked first and without a context, as
+ * bmfr_resolve_output checks it, then source and the guides, then the context.
+ * BMFR_ERROR_INVALID_ARGUMENT: source not one of the two values; NULL g or
+ * albedo; exactly one of normals and a position source (positions or depth)
+ * given; NULL frame_normals or frame_positions in guided mode; a limit that
+ * is not finite or not > 0; a guide plane, a frame plane or stats not aligned
+ * to its element; then, with a context: NULL ctx, no processed frame yet, a
+ * pending _interior without its _border, a size outside W <= Wd <= 4 W,
+ * H <= Hd <= 4 H, or the mapped Wd x Hd rectangle not inside the surface.
+ * BMFR_ERROR_UNSUPPORTED: a surface format outside the five listed, a guide
+ * format not listed for its plane, a tiled context.  Nothing is written and
+ * nothing is enqueued when an error is returned. */
+typedef struct bmfr_upsample_guides {  /* the renderer's display-resolution G-buffer: Wd x Hd, row stride Wd */
+    int width, height;                 /* Wd, Hd:  W <= Wd <= 4 W,  H <= Hd <= 4 H */
+    const void *albedo;   int albedo_format;   /* F32X3 | F16X4 | UNORM8X4; required */
+    const void *normals;  int normal_format;   /* F32X3 | F16X4 | OCT_SNORM16X2; nullable */
+    const float *positions;            /* F32X3 world positions, or NULL and: */
+    const float *depth;                /* f32 clip-space z / w, with */
+    float inv_view_proj[16];           /* column-major, and */
+    float pixel_offset[2];             /* the display G-buffer's own jitter */
+    float plane_limit_squared;         /* rule 3 */
+    float normal_limit_squared;
+} bmfr_upsample_guides;
+typedef enum bmfr_upsample_source { BMFR_UPSAMPLE_HDR = 0, BMFR_UPSAMPLE_TONEMAPPED = 1 } bmfr_upsample_source;
+
+/* Zeroes *g; both limits = the values the kernels see for cfg's
+ * position_limit_squared and normal_limit_squared (float of their "%g" text;
+ * cfg = NULL: of bmfr_config_default's). */
+void bmfr_upsample_guides_default(bmfr_upsample_guides *g, const bmfr_config *cfg);
+bmfr_status bmfr_upsample_output(bmfr_ctx *ctx, void *stream, int source,
+    const void *frame_normals, const void *frame_positions,   /* the frame's planes as given to bmfr_process_frame */
+    const bmfr_upsample_guides *g, const bmfr_surface *dst, uint32_t *stats /* device, nullable */);
+
 /* ---- Firefly pre-filter: an outlier clamp ahead of the block fit ----
  * (no reference counterpart: the reference's dataset is clean.  A renderer's
  * 1-spp buffers are not: one firefly is a huge residual in a 32x32 block's
