@@ -19,7 +19,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["bmfr_kernels.hip", "bmfr_fused.hip", "bmfr_fused_cols.hip", "bmfr_fused_cols_f32.hip", "bmfr_capi.hip",
            "bmfr_fused_plane.hip", "bmfr_fused_cols_plane.hip", "bmfr_fused_cols_f32_plane.hip",
            "bmfr_exchange.hip", "bmfr_prepare.hip", "bmfr_resolve.hip", "bmfr_firefly.hip",
-           "bmfr_upsample.hip", "bmfr_synth.hip",
+           "bmfr_upsample.hip", "bmfr_display_taa.hip", "bmfr_synth.hip",
            "bmfr_generic_ns1.hip", "bmfr_generic_ns2.hip", "bmfr_generic_ns3.hip", "bmfr_generic_ns4.hip",
            "bmfr_generic_aux_ns1.hip", "bmfr_generic_aux_ns2.hip", "bmfr_generic_aux_ns3.hip",
            "bmfr_generic_aux_ns4.hip"]

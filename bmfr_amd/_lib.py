@@ -140,6 +140,23 @@ class UpsampleGuides(C.Structure):
     ]
 
 
+class Plane(C.Structure):
+    """bmfr_plane: a display-resolution colour plane of bmfr_display_taa (include/bmfr.h)."""
+    _fields_ = [("data", C.c_void_p), ("format", C.c_int), ("pitch", C.c_size_t)]
+
+
+class DisplayTaaArgs(C.Structure):
+    """bmfr_display_taa_args: the planes and parameters of bmfr_display_taa (include/bmfr.h)."""
+    _fields_ = [
+        ("width", C.c_int), ("height", C.c_int),
+        ("current", Plane), ("history", Plane), ("result", Plane),
+        ("prev_pixel", C.c_void_p),
+        ("motion", C.c_void_p), ("motion_format", C.c_int),
+        ("motion_scale", C.c_float * 2), ("motion_at_pixel_centre", C.c_int), ("pixel_offset", C.c_float * 2),
+        ("blend_alpha", C.c_float), ("reset", C.c_int),
+    ]
+
+
 class FireflyParams(C.Structure):
     """bmfr_firefly_params: the rule of bmfr_suppress_fireflies (include/bmfr.h)."""
     _fields_ = [("threshold", C.c_float), ("radius", C.c_int), ("floor", C.c_float), ("replace_nonfinite", C.c_int)]
@@ -181,6 +198,8 @@ SIGNATURES = {
     "bmfr_resolve_output": (_I, [_P, _P, _I, _P, C.POINTER(Surface)]),
     "bmfr_upsample_guides_default": (None, [C.POINTER(UpsampleGuides), C.POINTER(Config)]),
     "bmfr_upsample_output": (_I, [_P, _P, _I, _P, _P, C.POINTER(UpsampleGuides), C.POINTER(Surface), _P]),
+    "bmfr_display_taa_default": (None, [C.POINTER(DisplayTaaArgs), C.POINTER(Config)]),
+    "bmfr_display_taa": (_I, [_P, _P, C.POINTER(DisplayTaaArgs), C.POINTER(Surface)]),
     "bmfr_firefly_default": (None, [C.POINTER(FireflyParams)]),
     "bmfr_suppress_fireflies": (_I, [_P, _P, _P, _P, C.POINTER(FireflyParams), _P]),
     "bmfr_halo_copy": (_I, [_P, _P, C.POINTER(C.c_int), _I, _P, _I, C.POINTER(C.c_size_t)]),

@@ -19,6 +19,7 @@
 #include "bmfr_prepare.h"
 #include "bmfr_resolve.h"
 #include "bmfr_upsample.h"
+#include "bmfr_display_taa.h"
 
 using bmfr::Params;
 
@@ -1231,6 +1232,101 @@ bmfr_status bmfr_upsample_output(bmfr_ctx* c, void* stream, int source, const vo
     a.dy_step = d->flip_y ? -1 : 1;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_upsample(a, as_stream(stream)));
+}
+
+// ------------------------------------- display-resolution TAA ----
+void bmfr_display_taa_default(bmfr_display_taa_args* a, const bmfr_config* cfg) {
+    if (!a) return;
+    std::memset(a, 0, sizeof *a);
+    bmfr_config d;
+    if (!cfg) bmfr_config_default(&d, BMFR_BLOCK_EDGE_LENGTH, BMFR_BLOCK_EDGE_LENGTH);
+    a->blend_alpha = (cfg ? cfg : &d)->taa_blend_alpha;
+    a->motion_scale[0] = a->motion_scale[1] = 1.0f;
+}
+
+namespace {
+
+// A display-resolution plane's format, pitch and alignment (data non-NULL).
+bmfr_status check_plane(const bmfr_plane& p, int width) {
+    if (p.format != BMFR_FORMAT_F32X3 && p.format != BMFR_FORMAT_F16X4) return BMFR_ERROR_UNSUPPORTED;
+    const size_t bpp = p.format == BMFR_FORMAT_F16X4 ? 8 : 12, align = p.format == BMFR_FORMAT_F16X4 ? 8 : 4;
+    if (p.pitch < (size_t)width * bpp || p.pitch % align != 0 || !aligned_to(p.data, align) ||
+        p.pitch > (size_t)1 << 31)  // row * pitch stays inside 64 bits (check_surface's bound)
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    return BMFR_OK;
+}
+
+// The arguments and the placement in dst alone (no context, no device).
+bmfr_status check_display_taa_args(const bmfr_display_taa_args* a, const bmfr_surface* d) {
+    if (d) {
+        const bmfr_status st = check_surface(d);
+        if (st != BMFR_OK) return st;
+    }
+    if (!a || a->width <= 0 || a->height <= 0 || !a->current.data || !a->result.data)
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    const bool with_history = !a->reset && a->history.data;
+    for (const bmfr_plane* p : {&a->current, &a->history, &a->result}) {
+        if (!p->data) continue;  // history: a NULL plane's format and pitch are not looked at
+        const bmfr_status st = check_plane(*p, a->width);
+        if (st != BMFR_OK) return st;
+    }
+    if (with_history) {
+        if ((a->prev_pixel != nullptr) == (a->motion != nullptr)) return BMFR_ERROR_INVALID_ARGUMENT;
+        if (!format_listed(a->motion, a->motion_format, {BMFR_FORMAT_F32X2, BMFR_FORMAT_F16X2}))
+            return BMFR_ERROR_UNSUPPORTED;
+        if (!aligned_to(a->prev_pixel, 4) || !aligned_to(a->motion, 4)) return BMFR_ERROR_INVALID_ARGUMENT;
+    }
+    if (a->result.data == a->current.data || a->result.data == a->history.data) return BMFR_ERROR_INVALID_ARGUMENT;
+    if (!std::isfinite(a->blend_alpha)) return BMFR_ERROR_INVALID_ARGUMENT;
+    if (d) {  // the Wd x Hd frame's rectangle in the surface (64-bit: origins are the caller's)
+        const long long x0 = d->origin_x, y0 = d->origin_y;
+        if (x0 < 0 || y0 < 0 || x0 + a->width > d->width || y0 + a->height > d->height)
+            return BMFR_ERROR_INVALID_ARGUMENT;
+    }
+    return BMFR_OK;
+}
+
+}  // namespace
+
+bmfr_status bmfr_display_taa(bmfr_ctx* c, void* stream, const bmfr_display_taa_args* args, const bmfr_surface* d) {
+    const bmfr_status st = check_display_taa_args(args, d);
+    if (st != BMFR_OK) return st;
+    if (!c) return BMFR_ERROR_INVALID_ARGUMENT;
+    const bool with_history = !args->reset && args->history.data;
+    bmfr::DisplayTaaArgs a{};
+    a.current = args->current.data;
+    a.history = with_history ? args->history.data : nullptr;
+    a.result = args->result.data;
+    a.prev_pixel = with_history ? args->prev_pixel : nullptr;
+    a.motion = with_history ? args->motion : nullptr;
+    a.current_pitch = (long long)args->current.pitch;
+    a.history_pitch = with_history ? (long long)args->history.pitch : 0;
+    a.result_pitch = (long long)args->result.pitch;
+    a.mscale[0] = args->motion_scale[0];
+    a.mscale[1] = args->motion_scale[1];
+    a.jx = args->pixel_offset[0];
+    a.jy1 = 1.0f - args->pixel_offset[1];
+    a.blend_a = args->blend_alpha;
+    a.blend_b = 1.0f - args->blend_alpha;
+    a.current_fmt = args->current.format;
+    a.history_fmt = args->history.format;
+    a.result_fmt = args->result.format;
+    a.motion_fmt = args->motion_format;
+    a.motion_centre = args->motion_at_pixel_centre != 0;
+    a.Wd = args->width;
+    a.Hd = args->height;
+    if (d) {
+        a.dst = d->data;
+        a.pitch = (long long)d->pitch;
+        a.alpha = d->alpha;
+        a.format = d->format;
+        a.bgr = d->bgr != 0;
+        a.dx0 = d->origin_x;
+        a.dy0 = d->flip_y ? d->origin_y + args->height - 1 : d->origin_y;  // display row 0 is the rectangle's last row when flipped
+        a.dy_step = d->flip_y ? -1 : 1;
+    }
+    DeviceGuard guard(c->device);
+    return hip_status(bmfr::launch_display_taa(a, as_stream(stream)));
 }
 
 // ------------------------------------------------- firefly pre-filter ----

@@ -738,6 +738,88 @@ class Denoiser(_Context):
                                             C.byref(g), C.byref(s), _ptr(stats)), "bmfr_upsample_output")
         return dst
 
+    # ---- Display-resolution TAA (include/bmfr.h bmfr_display_taa) ----
+    # (plane dtype, channels) -> bmfr_format
+    _TAA_PLANES = {(torch.float32, 3): _lib.FORMAT_F32X3, (torch.float16, 4): _lib.FORMAT_F16X4}
+    _MOTION_FORMATS = {torch.float32: _lib.FORMAT_F32X2, torch.float16: _lib.FORMAT_F16X2}
+
+    def _taa_plane(self, name: str, t, size=None) -> _lib.Plane:
+        """The bmfr_plane of a (Hd, Wd, 3) float32 or (Hd, Wd, 4) float16 tensor on
+        this GPU, packed pixels, the row stride free."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor, not {type(t).__name__}")
+        fmt = self._TAA_PLANES.get((t.dtype, t.shape[2])) if t.dim() == 3 else None
+        if fmt is None:
+            raise TypeError(f"{name} must be (rows, cols, 3) float32 or (rows, cols, 4) float16, not "
+                            f"{tuple(t.shape)} {t.dtype}")
+        ch = t.shape[2]
+        if t.numel() == 0 or tuple(t.stride()[1:]) != (ch, 1) or t.stride(0) < t.shape[1] * ch:
+            raise ValueError(f"{name} must have packed pixels and rows that do not overlap (strides {t.stride()}); "
+                             "only its row stride is free")
+        if size is not None and tuple(t.shape[:2]) != size:
+            raise ValueError(f"{name} must be {size[0]} x {size[1]} pixels like current, not {tuple(t.shape[:2])}")
+        if t.device.type != "cuda" or (t.device.index or 0) != self.device:
+            raise ValueError(f"{name} must live on cuda:{self.device}, not {t.device}")
+        return _lib.Plane(t.data_ptr(), fmt, t.stride(0) * t.element_size())
+
+    def display_taa_args(self, current, result, history=None, prev_pixel=None, motion=None, motion_scale=(1, 1),
+                         motion_at_pixel_centre=False, pixel_offset=(0.5, 0.5), blend_alpha=None, reset=False,
+                         dst=None, origin=(0, 0), flip_y=False, bgr=False, alpha=1.0):
+        """The checked arguments of bmfr_display_taa -> (bmfr_display_taa_args,
+        bmfr_surface or None); a caller that repeats a call keeps them.  Runs
+        before the call, which would read a wrong plane or write a wrong surface
+        out of bounds."""
+        a = _lib.DisplayTaaArgs()
+        self.lib.bmfr_display_taa_default(C.byref(a), C.byref(self.cfg.to_c()))
+        a.current = self._taa_plane("current", current)
+        size = tuple(current.shape[:2])
+        a.height, a.width = size
+        a.result = self._taa_plane("result", result, size)
+        if history is not None:
+            a.history = self._taa_plane("history", history, size)
+        pixels = a.width * a.height
+        if prev_pixel is not None:
+            self._check_plane("prev_pixel", prev_pixel, {torch.float32: (None, 2)}, pixels=pixels)
+            a.prev_pixel = prev_pixel.data_ptr()
+        if motion is not None:
+            a.motion_format = self._check_plane("motion", motion, {d: (f, 2) for d, f in self._MOTION_FORMATS.items()},
+                                                pixels=pixels)
+            a.motion = motion.data_ptr()
+        a.motion_scale[:] = [float(v) for v in motion_scale]
+        a.motion_at_pixel_centre = int(bool(motion_at_pixel_centre))
+        a.pixel_offset[:] = [float(v) for v in pixel_offset]
+        if blend_alpha is not None:
+            a.blend_alpha = float(blend_alpha)
+        a.reset = int(bool(reset))
+        s = None
+        if dst is not None:
+            s = self._surface(dst, origin, flip_y, bgr, alpha)
+            self._check_surface_device(dst)
+        return a, s
+
+    def display_taa(self, current, result, history=None, prev_pixel=None, motion=None, motion_scale=(1, 1),
+                    motion_at_pixel_centre=False, pixel_offset=(0.5, 0.5), blend_alpha=None, reset=False, dst=None,
+                    origin=(0, 0), flip_y=False, bgr=False, alpha=1.0, stream=None):
+        """bmfr_display_taa: the reference's TAA at display resolution, on
+        planes the caller owns, in one kernel launch.  current: this frame's
+        display-resolution colour, e.g. the tensor upsample(source=
+        "tonemapped") wrote; history: the previous call's result (None: no
+        history, as reset); result: written, the next call's history.  Each is
+        a CUDA tensor (Hd, Wd, 3) float32 or (Hd, Wd, 4) float16 (RGBA16F)
+        whose row stride is the pitch.  prev_pixel: float32, Hd * Wd * 2, the
+        previous position of each display pixel in process_frame's prev_pixel
+        convention at display size; or motion: float32 / float16 vectors with
+        motion_scale, motion_at_pixel_centre and pixel_offset as prepare takes
+        them.  blend_alpha: None = the configuration's taa_blend_alpha.  dst: a
+        surface as resolve takes it (origin, flip_y, bgr, alpha), written in
+        the same pass.  The context only names the device.  -> result."""
+        a, s = self.display_taa_args(current, result, history, prev_pixel, motion, motion_scale,
+                                     motion_at_pixel_centre, pixel_offset, blend_alpha, reset, dst, origin, flip_y,
+                                     bgr, alpha)
+        check(self.lib.bmfr_display_taa(self.handle, _stream(stream), C.byref(a), C.byref(s) if s is not None else None),
+              "bmfr_display_taa")
+        return result
+
     @property
     def region(self):
         """(x, y, width, height) of the image pixels this context's planes hold."""

@@ -747,8 +747,8 @@ bmfr_status bmfr_resolve_output(bmfr_ctx *ctx, void *stream, int source,
  * leaving out the taps that lie on another surface than the display pixel,
  * multiplies by the display-resolution albedo and writes a bmfr_surface, in one
  * kernel launch on `stream`.  It delivers the denoised, temporally accumulated,
- * remodulated image; it does NOT run TAA at display resolution:
- * display-resolution anti-aliasing stays the renderer's.
+ * remodulated image; it does not itself run TAA at display resolution:
+ * bmfr_display_taa, below, takes the surface it wrote and does.
  *
  * Planes.  The guides cover Wd x Hd with row stride Wd, one element per pixel
  * in the plane's bmfr_format, device memory aligned to the element (4 bytes;
@@ -844,6 +844,142 @@ void bmfr_upsample_guides_default(bmfr_upsample_guides *g, const bmfr_config *cf
 bmfr_status bmfr_upsample_output(bmfr_ctx *ctx, void *stream, int source,
     const void *frame_normals, const void *frame_positions,   /* the frame's planes as given to bmfr_process_frame */
     const bmfr_upsample_guides *g, const bmfr_surface *dst, uint32_t *stats /* device, nullable */);
+
+/* ---- Display-resolution TAA: anti-aliasing what the renderer shows ----
+ * (the reference's taa kernel, bmfr.cl:860-974, on planes the caller owns.)
+ *
+ * The library's own TAA (K2) runs at the resolution the frame was traced at.
+ * A renderer that traces at W x H and shows Wd x Hd shows what
+ * bmfr_upsample_output wrote, and its display-resolution albedo is rasterised
+ * with a moving jitter: every texture and geometry edge crawls.
+ * bmfr_display_taa applies the reference's TAA to that image: `current` (this
+ * frame's display-resolution colour), `history` (the previous call's result)
+ * and a display-resolution reprojection plane give `result`, and, in the same
+ * pass, the presentable surface `dst` -- one kernel launch on `stream`.  The
+ * caller ping-pongs two planes: this call's `result` is the next call's
+ * `history`.  With dst the low-resolution frame order needs no further resolve
+ * call: prepare -> (firefly) -> frame -> upsample (tone-mapped, into an F16X4
+ * or F32X3 surface) -> display TAA (dst = the swapchain image).
+ *
+ * The colour space is the caller's.  The reference clamps tone-mapped values,
+ * so BMFR_UPSAMPLE_TONEMAPPED is the intended `current`.
+ *
+ * Planes.  current, history and result are bmfr_plane: Wd x Hd pixels, F32X3
+ * or F16X4 (4th component ignored when read; half values widen exactly), rows
+ * `pitch` bytes apart, device memory aligned to the element (4 bytes; 8 for
+ * F16X4), each in its own format, a pitch at most 2^31 bytes.  result must
+ * not overlap current or history, and dst must not overlap any of the three:
+ * the kernel reads neighbours and taps that another thread's store would
+ * overwrite.  Only result.data equal to current.data or history.data is
+ * detected and refused; any other overlap is undefined.  prev_pixel is an F32X2 plane of Wd x Hd entries with row stride Wd:
+ * bmfr_frame_inputs.prev_pixel's convention with (W, H) = (Wd, Hd), i.e.
+ *     pfx = u * Wd - jx,      pfy = v * Hd - (1 - jy),
+ * (u, v) the previous frame's screen position of the display pixel's surface
+ * point and (jx, jy) the display G-buffer's current jitter.  Or prev_pixel is
+ * NULL and `motion` holds display-resolution motion vectors, with
+ * motion_format, motion_scale, motion_at_pixel_centre and pixel_offset exactly
+ * bmfr_gbuffer's fields and rule.
+ *
+ * Arithmetic: the reference's, as K2 computes it.  Every line is one f32
+ * operation rounded once, associated as written, never contracted, with
+ * division correctly rounded; min / max ignore a NaN operand (and order -0
+ * below +0).  The two colour transforms are the reference's dot():
+ *     ycocg(c) = (dot(c, (1, 2, 1)), dot(c, (2, 0, -2)), dot(c, (-1, 2, -1)))
+ *     rgb(c)   = (dot(c, (.25, .25, -.25)), dot(c, (.25, 0, .25)), dot(c, (.25, -.25, -.25)))
+ *     dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x))
+ * -- every coefficient is a power of two, so each product is exact and a dot
+ * is two rounded additions wherever no product overflows or underflows.  For
+ * display pixel (X, Y), W = Wd, H = Hd, a = blend_alpha:
+ *
+ *  1. Own colour.  me = current[Y][X].
+ *  2. Previous position.  (pfx, pfy) = prev_pixel[Y][X], or from motion[Y][X]
+ *     the "prev_pixel <- motion" lines of bmfr_prepare_frame with (x, y) =
+ *     (X, Y) and (jx, jy) = pixel_offset.
+ *  3. Off-screen test.  flx = floorf(pfx), fly = floorf(pfy).  If reset, or
+ *     history.data is NULL, or  flx < -1 || fly < -1 || flx >= float(W) ||
+ *     fly >= float(H)  (compared as floats; a NaN compares false and goes on,
+ *     as in K2):  v = me, and rules 4-6 do not apply.
+ *  4. Neighbourhood bounds (bmfr.cl:893-920).  Over the pixels (X + dx,
+ *     Y + dy), dx, dy in -1..1, that lie inside the image, s = ycocg(current):
+ *     mnb / mxb = the minimum / maximum over all of them (the box), mnc / mxc
+ *     over those with dx = 0 or dy = 0 (the cross), per component, each
+ *     starting from +inf / -inf.
+ *  5. History (bmfr.cl:925-966).
+ *       ix = (int)min(max(flx, -2.0f), float(W) + 1.0f);   iy likewise with H
+ *       fx = pfx - flx;  fy = pfy - fly;  omx = 1.0f - fx;  omy = 1.0f - fy
+ *     Taps k = (i, j) in the order 00, 10, 01, 11 at history pixel
+ *     (ix + i, iy + j) with weight  w_k = (i ? fx : omx) * (j ? fy : omy).
+ *     A tap enters when  (i ? ix < W - 1 : ix >= 0) && (j ? iy < H - 1 : iy >= 0):
+ *       prev = prev + w_k * history_k   per channel;   total = total + w_k
+ *     both starting from 0.  A tap of weight 0 is multiplied in, as in the
+ *     reference: a NaN or inf history value reaches prev.  (Past rule 3 a
+ *     tap that enters lies inside the plane, except for a NaN pfx or pfy:
+ *     then the nearest pixel inside is read, and every weight is NaN.)  Then
+ *       prev = prev / total;   py = ycocg(prev)
+ *  6. Clamp and blend (bmfr.cl:922-973).  Per component
+ *       lo = (mnb + mnc) / 2.0f;   hi = (mxb + mxc) / 2.0f
+ *       cl = min(max(py, lo), hi)                  (a NaN py becomes lo)
+ *       pr = rgb(cl);   b = 1.0f - a;   v = a * me + b * pr
+ *     so a NaN in history does not survive a frame whose current
+ *     neighbourhood is finite.
+ *  7. Outputs.  result[Y][X] = the bits of v (F32X3), or (half)v rounded to
+ *     nearest even with 4th component (half)1 (F16X4).  A non-NULL dst
+ *     receives the f32 v -- not the half-rounded one -- encoded exactly as
+ *     bmfr_resolve_output encodes it (five formats, bgr, alpha) at surface
+ *     pixel (origin_x + X, origin_y + (flip_y ? Hd - 1 - Y : Y)).  Nothing
+ *     else of dst, and nothing of result's pitch padding, is written.
+ *
+ * With blend_alpha = 1 the result is current wherever pr is finite; with
+ * reset = 1 (the reference's frame 0 -- a camera cut, the first frame, a
+ * resized window) or history.data NULL it is current bit for bit, and
+ * history, prev_pixel and motion are not read.
+ *
+ * Launch and state.  One kernel on `stream`; the caller orders it after the
+ * writer of `current` (the same stream, or an event).  The context only names
+ * the device: the call reads and changes no context state, no frame status and
+ * nothing bmfr_frame_status waits for; it is legal before any frame and on any
+ * context, tiled ones included, and width x height is independent of the
+ * context's size.
+ *
+ * Out of scope: fusing with bmfr_upsample_output (the clamp needs the nine
+ * neighbours' finished values); display planes tiled over several GPUs; the
+ * bmfr_host program and the stage API, which keep the reference's one
+ * resolution.
+ *
+ * Errors, in this order; nothing is enqueued or written when one is returned.
+ * A non-NULL dst is checked first, as bmfr_resolve_output checks it, without a
+ * context.  BMFR_ERROR_INVALID_ARGUMENT: NULL a; width or height <= 0; NULL
+ * current.data or result.data.  Then per plane (current, history if its data
+ * is non-NULL, result): BMFR_ERROR_UNSUPPORTED for a format other than F32X3 /
+ * F16X4; BMFR_ERROR_INVALID_ARGUMENT for a pitch below width * bytes per
+ * pixel or above 2^31, or a data pointer or pitch not a multiple of the element's alignment
+ * (4 for F32X3, 8 for F16X4).  Then, unless the call runs without history
+ * (reset, or NULL history.data, which needs and looks at neither):
+ * BMFR_ERROR_INVALID_ARGUMENT for both or neither of prev_pixel and motion,
+ * BMFR_ERROR_UNSUPPORTED for a motion_format other than F32X2 / F16X2,
+ * BMFR_ERROR_INVALID_ARGUMENT for a prev_pixel or motion pointer not a
+ * multiple of 4.  Then BMFR_ERROR_INVALID_ARGUMENT: result.data equal to
+ * current.data or history.data; blend_alpha not finite; the Wd x Hd rectangle
+ * not inside dst; NULL ctx. */
+typedef struct bmfr_plane { void *data; int format; size_t pitch; } bmfr_plane;  /* F32X3 | F16X4, Wd x Hd, rows `pitch` bytes apart */
+
+typedef struct bmfr_display_taa_args {
+    int width, height;            /* Wd, Hd > 0; independent of the context's size */
+    bmfr_plane current;           /* this frame's display-resolution colour, e.g. the surface bmfr_upsample_output wrote */
+    bmfr_plane history;           /* the previous call's `result`; data NULL: no history (as reset) */
+    bmfr_plane result;            /* written; the next call's history; must not be current's or history's memory */
+    const float *prev_pixel;      /* F32X2, Wd x Hd, stride Wd: bmfr_frame_inputs.prev_pixel's convention with (W, H) = (Wd, Hd); or NULL and: */
+    const void *motion; int motion_format;   /* F32X2 | F16X2 display-resolution motion vectors, with */
+    float motion_scale[2]; int motion_at_pixel_centre; float pixel_offset[2];   /* exactly bmfr_gbuffer's fields and rule */
+    float blend_alpha;            /* the reference's TAA_BLEND_ALPHA */
+    int reset;                    /* 1: the reference's frame 0: result = current */
+} bmfr_display_taa_args;
+
+/* Zeroes *a; blend_alpha = cfg's taa_blend_alpha (cfg = NULL: bmfr_config_default's);
+ * motion_scale = (1, 1). */
+void bmfr_display_taa_default(bmfr_display_taa_args *a, const bmfr_config *cfg);
+bmfr_status bmfr_display_taa(bmfr_ctx *ctx, void *stream, const bmfr_display_taa_args *a,
+    const bmfr_surface *dst /* nullable */);
 
 /* ---- Firefly pre-filter: an outlier clamp ahead of the block fit ----
  * (no reference counterpart: the reference's dataset is clean.  A renderer's
