@@ -1079,22 +1079,51 @@ void bmfr_surface_default(bmfr_surface* s) {
 
 namespace {
 
+// Bytes per pixel and alignment of a surface or display-plane format; false: not one.
+bool format_layout(int format, size_t* bpp, size_t* align) {
+    switch (format) {
+    case BMFR_FORMAT_F32X3: *bpp = 12, *align = 4; return true;
+    case BMFR_FORMAT_F16X4: *bpp = 8, *align = 8; return true;
+    case BMFR_FORMAT_UNORM8X4:
+    case BMFR_FORMAT_UNORM10X3A2: *bpp = 4, *align = 4; return true;
+    case BMFR_FORMAT_UNORM8X3: *bpp = 3, *align = 1; return true;
+    default: return false;
+    }
+}
+
+// Rows of `width` pixels of `format`, `pitch` bytes apart from `data`: pitch and alignment.
+bmfr_status check_rows(const void* data, size_t pitch, int format, int width) {
+    size_t bpp, align;
+    if (!format_layout(format, &bpp, &align)) return BMFR_ERROR_UNSUPPORTED;
+    if (pitch < (size_t)width * bpp || pitch % align != 0 || reinterpret_cast<uintptr_t>(data) % align != 0 ||
+        pitch > (size_t)1 << 31)  // row * pitch stays inside 64 bits
+        return BMFR_ERROR_INVALID_ARGUMENT;
+    return BMFR_OK;
+}
+
 // dst alone (no context, no device).
 bmfr_status check_surface(const bmfr_surface* d) {
     if (!d || !d->data || d->width <= 0 || d->height <= 0) return BMFR_ERROR_INVALID_ARGUMENT;
-    size_t bpp, align;
-    switch (d->format) {
-    case BMFR_FORMAT_F32X3: bpp = 12, align = 4; break;
-    case BMFR_FORMAT_F16X4: bpp = 8, align = 8; break;
-    case BMFR_FORMAT_UNORM8X4:
-    case BMFR_FORMAT_UNORM10X3A2: bpp = 4, align = 4; break;
-    case BMFR_FORMAT_UNORM8X3: bpp = 3, align = 1; break;
-    default: return BMFR_ERROR_UNSUPPORTED;
-    }
-    if (d->pitch < (size_t)d->width * bpp || d->pitch % align != 0 || reinterpret_cast<uintptr_t>(d->data) % align != 0 ||
-        d->pitch > (size_t)1 << 31)  // row * pitch stays inside 64 bits
-        return BMFR_ERROR_INVALID_ARGUMENT;
-    return BMFR_OK;
+    return check_rows(d->data, d->pitch, d->format, d->width);
+}
+
+// A w x h rectangle of a stage at (ox, oy) of d's frame of reference, whose
+// rows count from the top, or with flip_y from the bottom of a frame of
+// frame_height rows: false if it leaves the surface (64-bit: origins are the
+// caller's), else its placement -- row 0 is its last surface row when flipped.
+bool place_in_surface(const bmfr_surface* d, int ox, int oy, int w, int h, int frame_height, bmfr::SurfaceDst* s) {
+    const long long x0 = (long long)d->origin_x + ox;
+    const long long y0 = (long long)d->origin_y + (d->flip_y ? frame_height - oy - h : oy);
+    if (x0 < 0 || y0 < 0 || x0 + w > d->width || y0 + h > d->height) return false;
+    s->dst = d->data;
+    s->pitch = (long long)d->pitch;
+    s->alpha = d->alpha;
+    s->format = d->format;
+    s->bgr = d->bgr != 0;
+    s->dx0 = (int)x0;
+    s->dy0 = (int)(d->flip_y ? y0 + h - 1 : y0);
+    s->dy_step = d->flip_y ? -1 : 1;
+    return true;
 }
 
 // dst, source and albedo alone (no context, no device).
@@ -1117,27 +1146,16 @@ bmfr_status bmfr_resolve_output(bmfr_ctx* c, void* stream, int source, const voi
     const bool tiled = is_tiled(&g);
     const int tx = tiled ? g.tile_x : 0, ty = tiled ? g.tile_y : 0;
     const int tw = tiled ? g.tile_width : g.image_width, th = tiled ? g.tile_height : g.image_height;
-    // the tile's rectangle in the surface (64-bit: origins are the caller's)
-    const long long x0 = (long long)d->origin_x + tx;
-    const long long y0 = (long long)d->origin_y + (d->flip_y ? g.image_height - ty - th : ty);
-    if (x0 < 0 || y0 < 0 || x0 + tw > d->width || y0 + th > d->height) return BMFR_ERROR_INVALID_ARGUMENT;
     bmfr::ResolveArgs a{};
+    if (!place_in_surface(d, tx, ty, tw, th, g.image_height, &a.surf)) return BMFR_ERROR_INVALID_ARGUMENT;
     a.src = source == BMFR_RESOLVE_HDR ? c->acc[c->cur] : c->result[c->cur];
     a.albedo = source == BMFR_RESOLVE_HDR ? albedo : nullptr;
-    a.dst = d->data;
-    a.pitch = (long long)d->pitch;
-    a.alpha = d->alpha;
-    a.format = d->format;
     a.albedo_half = g.input_half != 0;
-    a.bgr = d->bgr != 0;
     a.rw = z.region_width;
     a.sx0 = tx - z.region_x;
     a.sy0 = ty - z.region_y;
     a.tw = tw;
     a.th = th;
-    a.dx0 = (int)x0;
-    a.dy0 = (int)(d->flip_y ? y0 + th - 1 : y0);  // tile row 0 is the rectangle's last row when flipped
-    a.dy_step = d->flip_y ? -1 : 1;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_resolve(a, as_stream(stream)));
 }
@@ -1195,10 +1213,8 @@ bmfr_status bmfr_upsample_output(bmfr_ctx* c, void* stream, int source, const vo
     const uintptr_t elem = cfg.input_half ? 2 : 4;
     if (guided && (!aligned_to(frame_normals, elem) || !aligned_to(frame_positions, elem)))
         return BMFR_ERROR_INVALID_ARGUMENT;
-    // the Wd x Hd frame's rectangle in the surface (64-bit: origins are the caller's)
-    const long long x0 = d->origin_x, y0 = d->origin_y;
-    if (x0 < 0 || y0 < 0 || x0 + Wd > d->width || y0 + Hd > d->height) return BMFR_ERROR_INVALID_ARGUMENT;
     bmfr::UpsampleArgs a{};
+    if (!place_in_surface(d, 0, 0, Wd, Hd, Hd, &a.surf)) return BMFR_ERROR_INVALID_ARGUMENT;
     a.acc = c->acc[c->cur];
     a.f_normals = guided ? frame_normals : nullptr;
     a.f_positions = guided ? frame_positions : nullptr;
@@ -1206,9 +1222,7 @@ bmfr_status bmfr_upsample_output(bmfr_ctx* c, void* stream, int source, const vo
     a.normals = g->normals;
     a.positions = g->positions;
     a.depth = g->depth;
-    a.dst = d->data;
     a.stats = guided ? stats : nullptr;
-    a.pitch = (long long)d->pitch;
     std::memcpy(a.m, g->inv_view_proj, sizeof a.m);
     a.jx = g->pixel_offset[0];
     a.jy1 = 1.0f - g->pixel_offset[1];
@@ -1216,20 +1230,14 @@ bmfr_status bmfr_upsample_output(bmfr_ctx* c, void* stream, int source, const vo
     a.ry = (float)H / (float)Hd;
     a.plane_limit_sq = g->plane_limit_squared;
     a.normal_limit_sq = g->normal_limit_squared;
-    a.alpha = d->alpha;
-    a.format = d->format;
     a.albedo_fmt = g->albedo_format;
     a.normal_fmt = g->normal_format;
     a.frame_half = cfg.input_half != 0;
     a.tonemapped = source == BMFR_UPSAMPLE_TONEMAPPED;
-    a.bgr = d->bgr != 0;
     a.W = W;
     a.H = H;
     a.Wd = Wd;
     a.Hd = Hd;
-    a.dx0 = (int)x0;
-    a.dy0 = (int)(d->flip_y ? y0 + Hd - 1 : y0);  // display row 0 is the rectangle's last row when flipped
-    a.dy_step = d->flip_y ? -1 : 1;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_upsample(a, as_stream(stream)));
 }
@@ -1249,14 +1257,10 @@ namespace {
 // A display-resolution plane's format, pitch and alignment (data non-NULL).
 bmfr_status check_plane(const bmfr_plane& p, int width) {
     if (p.format != BMFR_FORMAT_F32X3 && p.format != BMFR_FORMAT_F16X4) return BMFR_ERROR_UNSUPPORTED;
-    const size_t bpp = p.format == BMFR_FORMAT_F16X4 ? 8 : 12, align = p.format == BMFR_FORMAT_F16X4 ? 8 : 4;
-    if (p.pitch < (size_t)width * bpp || p.pitch % align != 0 || !aligned_to(p.data, align) ||
-        p.pitch > (size_t)1 << 31)  // row * pitch stays inside 64 bits (check_surface's bound)
-        return BMFR_ERROR_INVALID_ARGUMENT;
-    return BMFR_OK;
+    return check_rows(p.data, p.pitch, p.format, width);
 }
 
-// The arguments and the placement in dst alone (no context, no device).
+// The arguments and dst alone (no context, no device).
 bmfr_status check_display_taa_args(const bmfr_display_taa_args* a, const bmfr_surface* d) {
     if (d) {
         const bmfr_status st = check_surface(d);
@@ -1278,11 +1282,6 @@ bmfr_status check_display_taa_args(const bmfr_display_taa_args* a, const bmfr_su
     }
     if (a->result.data == a->current.data || a->result.data == a->history.data) return BMFR_ERROR_INVALID_ARGUMENT;
     if (!std::isfinite(a->blend_alpha)) return BMFR_ERROR_INVALID_ARGUMENT;
-    if (d) {  // the Wd x Hd frame's rectangle in the surface (64-bit: origins are the caller's)
-        const long long x0 = d->origin_x, y0 = d->origin_y;
-        if (x0 < 0 || y0 < 0 || x0 + a->width > d->width || y0 + a->height > d->height)
-            return BMFR_ERROR_INVALID_ARGUMENT;
-    }
     return BMFR_OK;
 }
 
@@ -1315,16 +1314,8 @@ bmfr_status bmfr_display_taa(bmfr_ctx* c, void* stream, const bmfr_display_taa_a
     a.motion_centre = args->motion_at_pixel_centre != 0;
     a.Wd = args->width;
     a.Hd = args->height;
-    if (d) {
-        a.dst = d->data;
-        a.pitch = (long long)d->pitch;
-        a.alpha = d->alpha;
-        a.format = d->format;
-        a.bgr = d->bgr != 0;
-        a.dx0 = d->origin_x;
-        a.dy0 = d->flip_y ? d->origin_y + args->height - 1 : d->origin_y;  // display row 0 is the rectangle's last row when flipped
-        a.dy_step = d->flip_y ? -1 : 1;
-    }
+    // d null: a.surf.dst stays null, no surface
+    if (d && !place_in_surface(d, 0, 0, a.Wd, a.Hd, a.Hd, &a.surf)) return BMFR_ERROR_INVALID_ARGUMENT;
     DeviceGuard guard(c->device);
     return hip_status(bmfr::launch_display_taa(a, as_stream(stream)));
 }

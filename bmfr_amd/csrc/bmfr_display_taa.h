@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmfr_pixel_io.h"
+
 namespace bmfr {
 
 // Kernel arguments of the display-resolution TAA (include/bmfr.h, bmfr_display_taa_args /
@@ -14,20 +16,14 @@ struct DisplayTaaArgs {
     void* result;
     const float* prev_pixel; // with history: this (f32x2, stride Wd) or motion
     const void* motion;
-    void* dst;               // surface pixel (0, 0); null: no surface
     long long current_pitch, history_pitch, result_pitch;
-    long long pitch;         // bytes between surface rows
+    SurfaceDst surf;         // the Wd x Hd frame in the surface; surf.dst null: no surface
     float mscale[2];         // motion_scale
     float jx, jy1;           // pixel_offset[0], 1.0f - pixel_offset[1]
     float blend_a, blend_b;  // blend_alpha, 1.0f - blend_alpha
-    float alpha;             // the surface's
     int current_fmt, history_fmt, result_fmt;  // BMFR_FORMAT_F32X3 | BMFR_FORMAT_F16X4
     int motion_fmt, motion_centre;
-    int format;              // bmfr_format of the surface
-    int bgr;
     int Wd, Hd;
-    int dx0, dy0;            // surface pixel of display pixel (0, 0)
-    int dy_step;             // +1, or -1 with flip_y: surface row of display row Y is dy0 + Y * dy_step
 };
 
 // One launch.

@@ -26,6 +26,7 @@
 // run-time switches.  No LDS.
 #include "../../include/bmfr.h"
 #include "bmfr_display_taa.h"
+#include "bmfr_pixel_io.h"
 
 namespace bmfr {
 namespace {
@@ -37,42 +38,16 @@ struct f3 {
     float x, y, z;
 };
 
-// bytes per pixel / natural alignment of a surface format
-template <int FMT>
-constexpr int kBpp = FMT == BMFR_FORMAT_F32X3 ? 12 : FMT == BMFR_FORMAT_F16X4 ? 8 : FMT == BMFR_FORMAT_UNORM8X3 ? 3 : 4;
-template <int FMT>
-constexpr int kNatural = FMT == BMFR_FORMAT_F16X4 ? 8 : FMT == BMFR_FORMAT_UNORM8X3 ? 1 : 4;
-
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void ld_bytes(const char* p, uint32_t* w) {
-    __builtin_memcpy(w, __builtin_assume_aligned(p, ALIGN), BYTES);
-}
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void st_bytes(char* p, const uint32_t* w) {
-    __builtin_memcpy(__builtin_assume_aligned(p, ALIGN), w, BYTES);
-}
-__device__ __forceinline__ float half_to_float(uint32_t bits) {
-    return (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
-}
-__device__ __forceinline__ uint32_t float_to_half(float v) {
-    return __builtin_bit_cast(uint16_t, (_Float16)v);  // round to nearest even; overflow -> inf
-}
-// c = v > 0 ? (v < 1 ? v : 1) : 0;  q = (uint)floorf(c * scale + 0.5f)
-__device__ __forceinline__ uint32_t unorm(float v, float scale) {
-    const float c = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return (uint32_t)__builtin_floorf(c * scale + 0.5f);
-}
-
 // Pixel (x, y), inside the plane, of an F32X3 / F16X4 plane as f32.
 __device__ __forceinline__ f3 ld_plane(const void* base, long long pitch, int fmt, int x, int y) {
     const char* row = reinterpret_cast<const char*>(base) + (long long)y * pitch;
     if (fmt == BMFR_FORMAT_F32X3) {
         uint32_t w[3];
-        ld_bytes<12, 4>(row + (long long)x * 12, w);
+        ld_bytes<12, 4>(row, (long long)x * 12, w);
         return f3{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2])};
     }
     uint32_t w[2];
-    ld_bytes<8, 8>(row + (long long)x * 8, w);
+    ld_bytes<8, 8>(row, (long long)x * 8, w);
     return f3{half_to_float(w[0] & 0xffffu), half_to_float(w[0] >> 16), half_to_float(w[1] & 0xffffu)};
 }
 
@@ -81,33 +56,11 @@ __device__ __forceinline__ void st_plane(void* base, long long pitch, int fmt, i
     char* row = reinterpret_cast<char*>(base) + (long long)y * pitch;
     if (fmt == BMFR_FORMAT_F32X3) {
         const uint32_t w[3] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z)};
-        st_bytes<12, 4>(row + (long long)x * 12, w);
+        st_bytes<12, 4>(row, (long long)x * 12, w);
     } else {
         const uint32_t w[2] = {float_to_half(v.x) | (float_to_half(v.y) << 16), float_to_half(v.z) | (0x3c00u << 16)};
-        st_bytes<8, 8>(row + (long long)x * 8, w);
+        st_bytes<8, 8>(row, (long long)x * 8, w);
     }
-}
-
-// One pixel's value into the surface at p (bmfr_resolve.hip's encoding).
-template <int FMT>
-__device__ __forceinline__ void st_pixel(const float (&v)[3], float alpha, char* p) {
-    uint32_t o[(kBpp<FMT> + 3) / 4] = {};
-    if constexpr (FMT == BMFR_FORMAT_F32X3) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = __float_as_uint(v[k]);
-    } else if constexpr (FMT == BMFR_FORMAT_F16X4) {
-        o[0] = float_to_half(v[0]) | (float_to_half(v[1]) << 16);
-        o[1] = float_to_half(v[2]) | (float_to_half(alpha) << 16);
-    } else if constexpr (FMT == BMFR_FORMAT_UNORM8X4) {
-        o[0] = unorm(v[0], 255.0f) | (unorm(v[1], 255.0f) << 8) | (unorm(v[2], 255.0f) << 16) |
-               (unorm(alpha, 255.0f) << 24);
-    } else if constexpr (FMT == BMFR_FORMAT_UNORM10X3A2) {
-        o[0] = unorm(v[0], 1023.0f) | (unorm(v[1], 1023.0f) << 10) | (unorm(v[2], 1023.0f) << 20) |
-               (unorm(alpha, 3.0f) << 30);
-    } else {  // BMFR_FORMAT_UNORM8X3
-        o[0] = unorm(v[0], 255.0f) | (unorm(v[1], 255.0f) << 8) | (unorm(v[2], 255.0f) << 16);
-    }
-    st_bytes<kBpp<FMT>, kNatural<FMT>>(p, o);
 }
 
 // RGB <-> YCoCg, bmfr.cl:184-198: dot(), an fma chain (the coefficients are
@@ -157,35 +110,19 @@ __device__ __forceinline__ Row load_row(const DisplayTaaArgs& a, int X, int y) {
 }
 
 // (pfx, pfy) of display pixel (X, Y): the prev_pixel entry, or bmfr_prepare_frame's motion rule.
-__device__ __forceinline__ void previous_position(const DisplayTaaArgs& a, int X, int Y, float& pfx, float& pfy) {
+__device__ __forceinline__ void ld_previous_position(const DisplayTaaArgs& a, int X, int Y, float& pfx, float& pfy) {
     const long long i = (long long)Y * a.Wd + X;
     if (a.prev_pixel) {
         uint32_t w[2];
-        ld_bytes<8, 4>(reinterpret_cast<const char*>(a.prev_pixel) + i * 8, w);
+        ld_bytes<8, 4>(a.prev_pixel, i * 8, w);
         pfx = __uint_as_float(w[0]);
         pfy = __uint_as_float(w[1]);
         return;
     }
-    float mvx, mvy;
-    if (a.motion_fmt == BMFR_FORMAT_F32X2) {
-        uint32_t w[2];
-        ld_bytes<8, 4>(reinterpret_cast<const char*>(a.motion) + i * 8, w);
-        mvx = __uint_as_float(w[0]);
-        mvy = __uint_as_float(w[1]);
-    } else {  // BMFR_FORMAT_F16X2
-        uint32_t w;
-        ld_bytes<4, 4>(reinterpret_cast<const char*>(a.motion) + i * 4, &w);
-        mvx = half_to_float(w & 0xffffu);
-        mvy = half_to_float(w >> 16);
-    }
-    const float mx = mvx * a.mscale[0], my = mvy * a.mscale[1];
-    if (a.motion_centre) {
-        pfx = (((float)X + 0.5f) - mx) - a.jx;
-        pfy = (((float)Y + 0.5f) - my) - a.jy1;
-    } else {
-        pfx = (float)X - mx;
-        pfy = (float)Y - my;
-    }
+    float mv[2];
+    ld_motion(a.motion, a.motion_fmt, i, mv);
+    previous_position(mv[0], mv[1], a.mscale[0], a.mscale[1], a.motion_centre != 0, (float)X, (float)Y, a.jx, a.jy1,
+                      pfx, pfy);
 }
 
 // Rules 2-6 for display pixel (X, Y) given its three rows (a call with history).
@@ -194,7 +131,7 @@ __device__ __forceinline__ f3 taa_pixel(const DisplayTaaArgs& a, int X, int Y, c
     const int W = a.Wd, H = a.Hd;
     const f3 me = mid.me;
     float pfx, pfy;
-    previous_position(a, X, Y, pfx, pfy);
+    ld_previous_position(a, X, Y, pfx, pfy);
     const float flx = __builtin_floorf(pfx), fly = __builtin_floorf(pfy);
     // bmfr.cl:884-890, compared as floats (a NaN compares false and goes on, as in K2)
     if (flx < -1.f || fly < -1.f || flx >= (float)W || fly >= (float)H) return me;
@@ -242,10 +179,8 @@ template <int FMT>
 __device__ __forceinline__ void store(const DisplayTaaArgs& a, int X, int Y, f3 v) {
     st_plane(a.result, a.result_pitch, a.result_fmt, X, Y, v);
     if constexpr (FMT != kNoSurface) {
-        const float val[3] = {a.bgr ? v.z : v.x, v.y, a.bgr ? v.x : v.z};
-        char* p = reinterpret_cast<char*>(a.dst) + (long long)(a.dy0 + Y * a.dy_step) * a.pitch +
-                  (long long)(a.dx0 + X) * kBpp<FMT>;
-        st_pixel<FMT>(val, a.alpha, p);
+        const float val[3] = {a.surf.bgr ? v.z : v.x, v.y, a.surf.bgr ? v.x : v.z};
+        st_surface<FMT>(surface_pixel<FMT>(a.surf, X, Y), val, a.surf.alpha);
     }
 }
 
@@ -275,11 +210,6 @@ __global__ __launch_bounds__(kTileW * kWaves) void display_taa_kernel(const Disp
     }
 }
 
-template <int FMT>
-void launch(const DisplayTaaArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL(display_taa_kernel<FMT>, grid, dim3(kTileW, kWaves), 0, st, a);
-}
-
 }  // namespace
 
 hipError_t launch_display_taa(const DisplayTaaArgs& a, hipStream_t st) {
@@ -287,18 +217,15 @@ hipError_t launch_display_taa(const DisplayTaaArgs& a, hipStream_t st) {
     const int tile_h = kWaves * kRows;
     const int rows = (int)(((long long)a.Hd + tile_h - 1) / tile_h);
     const dim3 grid((unsigned)(((long long)a.Wd + kTileW - 1) / kTileW), rows < 65535 ? rows : 65535);
-    if (!a.dst) {
-        launch<kNoSurface>(a, grid, st);
+    const dim3 block(kTileW, kWaves);
+    if (!a.surf.dst) {
+        hipLaunchKernelGGL(display_taa_kernel<kNoSurface>, grid, block, 0, st, a);
         return hipGetLastError();
     }
-    switch (a.format) {
-    case BMFR_FORMAT_F32X3: launch<BMFR_FORMAT_F32X3>(a, grid, st); break;
-    case BMFR_FORMAT_F16X4: launch<BMFR_FORMAT_F16X4>(a, grid, st); break;
-    case BMFR_FORMAT_UNORM8X4: launch<BMFR_FORMAT_UNORM8X4>(a, grid, st); break;
-    case BMFR_FORMAT_UNORM8X3: launch<BMFR_FORMAT_UNORM8X3>(a, grid, st); break;
-    case BMFR_FORMAT_UNORM10X3A2: launch<BMFR_FORMAT_UNORM10X3A2>(a, grid, st); break;
-    default: return hipErrorInvalidValue;
-    }
+    const bool listed = dispatch_surface_format(a.surf.format, [&](auto fmt) {
+        hipLaunchKernelGGL(display_taa_kernel<decltype(fmt)::value>, grid, block, 0, st, a);
+    });
+    if (!listed) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

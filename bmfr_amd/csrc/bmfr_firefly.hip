@@ -29,6 +29,7 @@
 
 #include "../../include/bmfr.h"
 #include "bmfr_firefly.h"
+#include "bmfr_pixel_io.h"
 
 namespace bmfr {
 namespace {
@@ -36,52 +37,6 @@ namespace {
 constexpr int kFireflyThreads = 256;
 constexpr int kCols = 16, kRows = 16;  // groups per tile row, tile rows
 constexpr int kMaxGroups = 2048;       // work-groups of a launch, about: 8 per CU
-template <class T>
-constexpr int kGroup = sizeof(T) == 4 ? 4 : 8;
-
-// BYTES at base + off into / out of 32-bit words (the last word may be partial).
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void ld_bytes(const void* base, uint32_t off, uint32_t* w) {
-    const char* p = reinterpret_cast<const char*>(base) + off;
-    __builtin_memcpy(w, __builtin_assume_aligned(p, ALIGN), BYTES);
-}
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void st_bytes(void* base, uint32_t off, const uint32_t* w) {
-    char* p = reinterpret_cast<char*>(base) + off;
-    __builtin_memcpy(__builtin_assume_aligned(p, ALIGN), w, BYTES);
-}
-
-// N pixels of a float3 / half3 plane from pixel `first`, as element bits
-// (f32, or half in the low 16); WIDE: the run is 16-byte aligned.
-template <class T, int N, bool WIDE>
-__device__ __forceinline__ void ld_elems(const void* base, uint32_t first, uint32_t* e) {
-    constexpr int BYTES = N * 3 * (int)sizeof(T);
-    uint32_t w[(BYTES + 3) / 4] = {};
-    ld_bytes<BYTES, WIDE ? 16 : (int)sizeof(T)>(base, first * (3u * sizeof(T)), w);
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) e[i] = sizeof(T) == 4 ? w[i] : (w[i >> 1] >> (16 * (i & 1))) & 0xffffu;
-}
-template <class T, int N, bool WIDE>
-__device__ __forceinline__ void st_elems(void* base, uint32_t first, const uint32_t* e) {
-    constexpr int BYTES = N * 3 * (int)sizeof(T);
-    uint32_t w[(BYTES + 3) / 4] = {};
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) {
-        if constexpr (sizeof(T) == 4) w[i] = e[i];
-        else w[i >> 1] |= e[i] << (16 * (i & 1));
-    }
-    st_bytes<BYTES, WIDE ? 16 : (int)sizeof(T)>(base, first * (3u * sizeof(T)), w);
-}
-template <class T>
-__device__ __forceinline__ float decode(uint32_t bits) {
-    if constexpr (sizeof(T) == 4) return __uint_as_float(bits);
-    else return (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
-}
-template <class T>
-__device__ __forceinline__ uint32_t encode(float v) {
-    if constexpr (sizeof(T) == 4) return __float_as_uint(v);
-    else return __builtin_bit_cast(uint16_t, (_Float16)v);  // round to nearest even
-}
 
 __device__ __forceinline__ bool finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }  // false for NaN
 // Y of a pixel's element bits

@@ -14,103 +14,21 @@
 // (bmfr_create bounds planes at 4 GiB).  Input formats are wave-uniform
 // run-time switches; the output element type is a template parameter.  No LDS.
 #include "../../include/bmfr.h"
+#include "bmfr_pixel_io.h"
 #include "bmfr_prepare.h"
 
 namespace bmfr {
 namespace {
 
 constexpr int kPrepareThreads = 256;
-template <class OUT>
-constexpr int kGroup = sizeof(OUT) == 4 ? 4 : 8;
 
-// Alignment of an access of BYTES at a group's (WIDE) or a pixel's offset;
-// NATURAL: the element's own alignment.
-template <int BYTES, bool WIDE, int NATURAL>
-constexpr int kAlign = !WIDE ? NATURAL : (BYTES % 16 == 0 ? 16 : (BYTES % 8 == 0 ? 8 : NATURAL));
-
-// BYTES at base + off into / out of 32-bit words (the last word may be partial).
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void ld_bytes(const void* base, uint32_t off, uint32_t* w) {
-    const char* p = reinterpret_cast<const char*>(base) + off;
-    __builtin_memcpy(w, __builtin_assume_aligned(p, ALIGN), BYTES);
-}
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void st_bytes(void* base, uint32_t off, const uint32_t* w) {
-    char* p = reinterpret_cast<char*>(base) + off;
-    __builtin_memcpy(__builtin_assume_aligned(p, ALIGN), w, BYTES);
-}
-
-// 16-bit element k of packed words.
-__device__ __forceinline__ uint32_t u16_at(const uint32_t* w, int k) { return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu; }
-__device__ __forceinline__ float half_to_float(uint32_t bits) {
-    return (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
-}
-
-// One output element's bits (f32, or half in the low 16) <-> f32.
-template <class OUT>
-__device__ __forceinline__ uint32_t encode(float v) {
-    if constexpr (sizeof(OUT) == 4) return __float_as_uint(v);
-    else return __builtin_bit_cast(uint16_t, (_Float16)v);
-}
-template <class OUT>
-__device__ __forceinline__ float decode(uint32_t bits) {
-    if constexpr (sizeof(OUT) == 4) return __uint_as_float(bits);
-    else return half_to_float(bits);
-}
-
-// N pixels of a float3 / half3 plane from pixel `first`, as element bits.
-template <class OUT, int N, bool WIDE>
-__device__ __forceinline__ void ld_elems(const void* base, uint32_t first, uint32_t (&e)[N * 3]) {
-    constexpr int BYTES = N * 3 * (int)sizeof(OUT);
-    uint32_t w[(BYTES + 3) / 4] = {};
-    ld_bytes<BYTES, kAlign<BYTES, WIDE, (int)sizeof(OUT)>>(base, first * (3u * sizeof(OUT)), w);
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) e[i] = sizeof(OUT) == 4 ? w[i] : u16_at(w, i);
-}
-template <class OUT, int N, bool WIDE>
-__device__ __forceinline__ void st_elems(void* base, uint32_t first, const uint32_t (&e)[N * 3]) {
-    constexpr int BYTES = N * 3 * (int)sizeof(OUT);
-    uint32_t w[(BYTES + 3) / 4] = {};
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) {
-        if constexpr (sizeof(OUT) == 4) w[i] = e[i];
-        else w[i >> 1] |= e[i] << (16 * (i & 1));
-    }
-    st_bytes<BYTES, kAlign<BYTES, WIDE, (int)sizeof(OUT)>>(base, first * (3u * sizeof(OUT)), w);
-}
+// N pixels' f32 values into a float3 / half3 plane from pixel `first`.
 template <class OUT, int N, bool WIDE>
 __device__ __forceinline__ void st_float3(void* base, uint32_t first, const float (&v)[N][3]) {
     uint32_t e[N * 3];
 #pragma unroll
     for (int i = 0; i < N * 3; ++i) e[i] = encode<OUT>(v[i / 3][i % 3]);
     st_elems<OUT, N, WIDE>(base, first, e);
-}
-
-// N pixels of a three-channel G-buffer plane (F32X3, F16X4, UNORM8X4) as f32.
-template <int N, bool WIDE>
-__device__ __forceinline__ void ld_channels(const void* base, int fmt, uint32_t first, float (&c)[N][3]) {
-    if (fmt == BMFR_FORMAT_F32X3) {
-        uint32_t w[N * 3];
-        ld_bytes<N * 12, kAlign<N * 12, WIDE, 4>>(base, first * 12u, w);
-#pragma unroll
-        for (int i = 0; i < N * 3; ++i) c[i / 3][i % 3] = __uint_as_float(w[i]);
-    } else if (fmt == BMFR_FORMAT_F16X4) {
-        uint32_t w[N * 2];
-        ld_bytes<N * 8, kAlign<N * 8, WIDE, 8>>(base, first * 8u, w);
-#pragma unroll
-        for (int i = 0; i < N * 3; ++i) c[i / 3][i % 3] = half_to_float(u16_at(w, 4 * (i / 3) + i % 3));
-    } else {  // BMFR_FORMAT_UNORM8X4
-        uint32_t w[N];
-        ld_bytes<N * 4, kAlign<N * 4, WIDE, 4>>(base, first * 4u, w);
-#pragma unroll
-        for (int i = 0; i < N * 3; ++i) c[i / 3][i % 3] = (float)((w[i / 3] >> (8 * (i % 3))) & 255u) / 255.0f;
-    }
-}
-
-// One octahedral snorm16 component.
-__device__ __forceinline__ float snorm16(uint32_t bits) {
-    const float e = (float)(int16_t)(uint16_t)bits / 32767.0f;
-    return e < -1.0f ? -1.0f : e;
 }
 
 // N consecutive pixels from flat region index `first`.
@@ -157,20 +75,7 @@ __device__ __forceinline__ void prepare_pixels(const PrepareArgs& a, uint32_t fi
             uint32_t w[N];
             ld_bytes<N * 4, kAlign<N * 4, WIDE, 4>>(a.normals, first * 4u, w);
 #pragma unroll
-            for (int p = 0; p < N; ++p) {
-                const float ex = snorm16(w[p] & 0xffffu), ey = snorm16(w[p] >> 16);
-                const float ax = __builtin_fabsf(ex), ay = __builtin_fabsf(ey);
-                const float z = (1.0f - ax) - ay;
-                float ox = ex, oy = ey;
-                if (z < 0.0f) {
-                    ox = (1.0f - ay) * (ex >= 0.0f ? 1.0f : -1.0f);
-                    oy = (1.0f - ax) * (ey >= 0.0f ? 1.0f : -1.0f);
-                }
-                const float len = __builtin_sqrtf((ox * ox + oy * oy) + z * z);
-                nrm[p][0] = ox / len;
-                nrm[p][1] = oy / len;
-                nrm[p][2] = z / len;
-            }
+            for (int p = 0; p < N; ++p) oct_decode(w[p], nrm[p]);
         } else {
             ld_channels<N, WIDE>(a.normals, a.normal_fmt, first, nrm);
         }
@@ -187,16 +92,8 @@ __device__ __forceinline__ void prepare_pixels(const PrepareArgs& a, uint32_t fi
             ld_bytes<N * 4, kAlign<N * 4, WIDE, 4>>(a.depth, first * 4u, w);
             const float fW = (float)a.W, fH = (float)a.H;
 #pragma unroll
-            for (int p = 0; p < N; ++p) {
-                const float depth = __uint_as_float(w[p]);
-                const float sx = fx[p] + a.jx, sy = fy[p] + a.jy1;
-                const float nx = (sx / fW) * 2.0f - 1.0f, ny = (sy / fH) * 2.0f - 1.0f;
-                float h[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) h[i] = ((a.m[i] * nx + a.m[4 + i] * ny) + a.m[8 + i] * depth) + a.m[12 + i];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) pos[p][i] = h[i] / h[3];
-            }
+            for (int p = 0; p < N; ++p)
+                position_from_depth(a.m, __uint_as_float(w[p]), fx[p], fy[p], a.jx, a.jy1, fW, fH, pos[p]);
         }
         st_float3<OUT, N, WIDE>(a.o_positions, first, pos);
     }
@@ -204,29 +101,13 @@ __device__ __forceinline__ void prepare_pixels(const PrepareArgs& a, uint32_t fi
     // motion vectors -> prev_pixel
     if (a.o_prev_pixel) {
         float mv[N][2];
-        if (a.motion_fmt == BMFR_FORMAT_F32X2) {
-            uint32_t w[N * 2];
-            ld_bytes<N * 8, kAlign<N * 8, WIDE, 8>>(a.motion, first * 8u, w);
-#pragma unroll
-            for (int i = 0; i < N * 2; ++i) mv[i / 2][i % 2] = __uint_as_float(w[i]);
-        } else {  // BMFR_FORMAT_F16X2
-            uint32_t w[N];
-            ld_bytes<N * 4, kAlign<N * 4, WIDE, 4>>(a.motion, first * 4u, w);
-#pragma unroll
-            for (int i = 0; i < N * 2; ++i) mv[i / 2][i % 2] = half_to_float(u16_at(w, i));
-        }
+        ld_motion<N, WIDE>(a.motion, a.motion_fmt, first, mv);
         uint32_t o[N * 2];
 #pragma unroll
         for (int p = 0; p < N; ++p) {
-            const float mx = mv[p][0] * a.mscale_x, my = mv[p][1] * a.mscale_y;
             float pfx, pfy;
-            if (a.motion_centre) {
-                pfx = ((fx[p] + 0.5f) - mx) - a.jx;
-                pfy = ((fy[p] + 0.5f) - my) - a.jy1;
-            } else {
-                pfx = fx[p] - mx;
-                pfy = fy[p] - my;
-            }
+            previous_position(mv[p][0], mv[p][1], a.mscale_x, a.mscale_y, a.motion_centre != 0, fx[p], fy[p], a.jx,
+                              a.jy1, pfx, pfy);
             o[2 * p] = __float_as_uint(pfx);
             o[2 * p + 1] = __float_as_uint(pfy);
         }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmfr_pixel_io.h"
+
 namespace bmfr {
 
 // Kernel arguments of the output back end (include/bmfr.h, bmfr_surface):
@@ -11,16 +13,11 @@ namespace bmfr {
 struct ResolveArgs {
     const float* src;    // the region's result or filtered_accumulated plane, f32x3, row stride rw
     const void* albedo;  // BMFR_RESOLVE_HDR: the region's albedo plane (f32x3, or half3: albedo_half); else null
-    void* dst;           // surface pixel (0, 0)
-    long long pitch;     // bytes between surface rows
-    float alpha;
-    int format;          // bmfr_format of the surface
-    int albedo_half, bgr;
+    SurfaceDst surf;     // the tile in the surface: rectangle row r is tile row r
+    int albedo_half;
     int rw;              // region row stride, pixels
     int sx0, sy0;        // the tile's first pixel, region coordinates
     int tw, th;          // tile size
-    int dx0, dy0;        // surface pixel of the tile's first pixel
-    int dy_step;         // +1, or -1 with flip_y: surface row of tile row r is dy0 + r * dy_step
     int wide;            // groups of 4 pixels with 16-byte source loads (set by the launcher)
 };
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bmfr_pixel_io.h"
+
 namespace bmfr {
 
 // Kernel arguments of the guided upsampler (include/bmfr.h, bmfr_upsample_guides /
@@ -16,20 +18,15 @@ struct UpsampleArgs {
     const void* normals;     // null: unguided
     const float* positions;  // guided: this or depth
     const float* depth;
-    void* dst;               // surface pixel (0, 0)
     uint32_t* stats;         // nullable
-    long long pitch;         // bytes between surface rows
+    SurfaceDst surf;         // the Wd x Hd frame in the surface
     float m[16];             // inv_view_proj, column-major
     float jx, jy1;           // pixel_offset[0], 1.0f - pixel_offset[1]
     float rx, ry;            // float(W) / float(Wd), float(H) / float(Hd)
     float plane_limit_sq, normal_limit_sq;
-    float alpha;
-    int format;              // bmfr_format of the surface
     int albedo_fmt, normal_fmt;
-    int frame_half, tonemapped, bgr;
+    int frame_half, tonemapped;
     int W, H, Wd, Hd;
-    int dx0, dy0;            // surface pixel of display pixel (0, 0)
-    int dy_step;             // +1, or -1 with flip_y: surface row of display row Y is dy0 + Y * dy_step
 };
 
 // One launch.

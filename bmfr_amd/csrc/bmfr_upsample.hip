@@ -18,6 +18,7 @@
 // template parameter; source, guided / unguided, the guide formats, bgr and
 // flip_y are wave-uniform run-time switches.  No LDS.
 #include "../../include/bmfr.h"
+#include "bmfr_pixel_io.h"
 #include "bmfr_powr.h"
 #include "bmfr_upsample.h"
 
@@ -26,97 +27,18 @@ namespace {
 
 constexpr int kTileW = 64, kTileH = 4;
 
-// bytes per pixel / natural alignment of a surface format
-template <int FMT>
-constexpr int kBpp = FMT == BMFR_FORMAT_F32X3 ? 12 : FMT == BMFR_FORMAT_F16X4 ? 8 : FMT == BMFR_FORMAT_UNORM8X3 ? 3 : 4;
-template <int FMT>
-constexpr int kNatural = FMT == BMFR_FORMAT_F16X4 ? 8 : FMT == BMFR_FORMAT_UNORM8X3 ? 1 : 4;
-
-// BYTES at p into / out of 32-bit words (the last word may be partial).
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void ld_bytes(const void* base, size_t off, uint32_t* w) {
-    const char* p = reinterpret_cast<const char*>(base) + off;
-    __builtin_memcpy(w, __builtin_assume_aligned(p, ALIGN), BYTES);
-}
-template <int BYTES, int ALIGN>
-__device__ __forceinline__ void st_bytes(char* p, const uint32_t* w) {
-    __builtin_memcpy(__builtin_assume_aligned(p, ALIGN), w, BYTES);
-}
-__device__ __forceinline__ float half_to_float(uint32_t bits) {
-    return (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
-}
-__device__ __forceinline__ uint32_t float_to_half(float v) {
-    return __builtin_bit_cast(uint16_t, (_Float16)v);  // round to nearest even; overflow -> inf
-}
-// c = v > 0 ? (v < 1 ? v : 1) : 0;  q = (uint)floorf(c * scale + 0.5f)
-__device__ __forceinline__ uint32_t unorm(float v, float scale) {
-    const float c = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return (uint32_t)__builtin_floorf(c * scale + 0.5f);
-}
-
-// Pixel i of a three-channel guide plane (F32X3, F16X4, UNORM8X4) as f32.
-__device__ __forceinline__ void ld_channels(const void* base, int fmt, size_t i, float (&c)[3]) {
-    if (fmt == BMFR_FORMAT_F32X3) {
-        uint32_t w[3];
-        ld_bytes<12, 4>(base, i * 12u, w);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] = __uint_as_float(w[k]);
-    } else if (fmt == BMFR_FORMAT_F16X4) {
-        uint32_t w[2];
-        ld_bytes<8, 8>(base, i * 8u, w);
-        c[0] = half_to_float(w[0] & 0xffffu);
-        c[1] = half_to_float(w[0] >> 16);
-        c[2] = half_to_float(w[1] & 0xffffu);
-    } else {  // BMFR_FORMAT_UNORM8X4
-        uint32_t w;
-        ld_bytes<4, 4>(base, i * 4u, &w);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] = (float)((w >> (8 * k)) & 255u) / 255.0f;
-    }
-}
-
-// One octahedral snorm16 component.
-__device__ __forceinline__ float snorm16(uint32_t bits) {
-    const float e = (float)(int16_t)(uint16_t)bits / 32767.0f;
-    return e < -1.0f ? -1.0f : e;
-}
-
 // Pixel i (byte offset i * 12, or i * 6 of a half3 plane) of a frame plane as f32.
 __device__ __forceinline__ void ld_frame(const void* base, bool half, uint32_t i, float (&c)[3]) {
+    uint32_t e[3];
     if (half) {
-        uint32_t w[2] = {};
-        ld_bytes<6, 2>(base, i * 6u, w);
-        c[0] = half_to_float(w[0] & 0xffffu);
-        c[1] = half_to_float(w[0] >> 16);
-        c[2] = half_to_float(w[1] & 0xffffu);
+        ld_elems<_Float16, 1, false>(base, i, e);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = half_to_float(e[k]);
     } else {
-        uint32_t w[3];
-        ld_bytes<12, 4>(base, i * 12u, w);
+        ld_elems<float, 1, false>(base, i, e);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] = __uint_as_float(w[k]);
+        for (int k = 0; k < 3; ++k) c[k] = __uint_as_float(e[k]);
     }
-}
-
-// One pixel's source value into the surface at p (bmfr_resolve.hip's encoding).
-template <int FMT>
-__device__ __forceinline__ void st_pixel(const float (&v)[3], float alpha, char* p) {
-    uint32_t o[(kBpp<FMT> + 3) / 4] = {};
-    if constexpr (FMT == BMFR_FORMAT_F32X3) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = __float_as_uint(v[k]);
-    } else if constexpr (FMT == BMFR_FORMAT_F16X4) {
-        o[0] = float_to_half(v[0]) | (float_to_half(v[1]) << 16);
-        o[1] = float_to_half(v[2]) | (float_to_half(alpha) << 16);
-    } else if constexpr (FMT == BMFR_FORMAT_UNORM8X4) {
-        o[0] = unorm(v[0], 255.0f) | (unorm(v[1], 255.0f) << 8) | (unorm(v[2], 255.0f) << 16) |
-               (unorm(alpha, 255.0f) << 24);
-    } else if constexpr (FMT == BMFR_FORMAT_UNORM10X3A2) {
-        o[0] = unorm(v[0], 1023.0f) | (unorm(v[1], 1023.0f) << 10) | (unorm(v[2], 1023.0f) << 20) |
-               (unorm(alpha, 3.0f) << 30);
-    } else {  // BMFR_FORMAT_UNORM8X3
-        o[0] = unorm(v[0], 255.0f) | (unorm(v[1], 255.0f) << 8) | (unorm(v[2], 255.0f) << 16);
-    }
-    st_bytes<kBpp<FMT>, kNatural<FMT>>(p, o);
 }
 
 // Display pixel (X, Y), inside the frame.
@@ -146,18 +68,7 @@ __device__ __forceinline__ void upsample_pixel(const UpsampleArgs& a, int X, int
         if (a.normal_fmt == BMFR_FORMAT_OCT_SNORM16X2) {
             uint32_t wd;
             ld_bytes<4, 4>(a.normals, di * 4u, &wd);
-            const float ex = snorm16(wd & 0xffffu), ey = snorm16(wd >> 16);
-            const float ax = __builtin_fabsf(ex), ay = __builtin_fabsf(ey);
-            const float z = (1.0f - ax) - ay;
-            float ox = ex, oy = ey;
-            if (z < 0.0f) {
-                ox = (1.0f - ay) * (ex >= 0.0f ? 1.0f : -1.0f);
-                oy = (1.0f - ax) * (ey >= 0.0f ? 1.0f : -1.0f);
-            }
-            const float len = __builtin_sqrtf((ox * ox + oy * oy) + z * z);
-            N[0] = ox / len;
-            N[1] = oy / len;
-            N[2] = z / len;
+            oct_decode(wd, N);
         } else {
             ld_channels(a.normals, a.normal_fmt, di, N);
         }
@@ -166,14 +77,7 @@ __device__ __forceinline__ void upsample_pixel(const UpsampleArgs& a, int X, int
         } else {
             uint32_t wd;
             ld_bytes<4, 4>(a.depth, di * 4u, &wd);
-            const float depth = __uint_as_float(wd);
-            const float sx = (float)X + a.jx, sy = (float)Y + a.jy1;
-            const float nx = (sx / (float)a.Wd) * 2.0f - 1.0f, ny = (sy / (float)a.Hd) * 2.0f - 1.0f;
-            float h[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) h[i] = ((a.m[i] * nx + a.m[4 + i] * ny) + a.m[8 + i] * depth) + a.m[12 + i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) P[i] = h[i] / h[3];
+            position_from_depth(a.m, __uint_as_float(wd), (float)X, (float)Y, a.jx, a.jy1, (float)a.Wd, (float)a.Hd, P);
         }
     }
 
@@ -223,14 +127,12 @@ __device__ __forceinline__ void upsample_pixel(const UpsampleArgs& a, int X, int
 #pragma unroll
         for (int c = 0; c < 3; ++c) val[c] = gamma_clamped(val[c]);
     }
-    if (a.bgr) {
+    if (a.surf.bgr) {
         const float t = val[0];
         val[0] = val[2];
         val[2] = t;
     }
-    char* p = reinterpret_cast<char*>(a.dst) + (long long)(a.dy0 + Y * a.dy_step) * a.pitch +
-              (long long)(a.dx0 + X) * kBpp<FMT>;
-    st_pixel<FMT>(val, a.alpha, p);
+    st_surface<FMT>(surface_pixel<FMT>(a.surf, X, Y), val, a.surf.alpha);
 }
 
 template <int FMT>
@@ -240,25 +142,16 @@ __global__ __launch_bounds__(kTileW * kTileH) void upsample_kernel(const Upsampl
     for (int Y = blockIdx.y * kTileH + threadIdx.y; Y < a.Hd; Y += gridDim.y * kTileH) upsample_pixel<FMT>(a, X, Y);
 }
 
-template <int FMT>
-void launch(const UpsampleArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL(upsample_kernel<FMT>, grid, dim3(kTileW, kTileH), 0, st, a);
-}
-
 }  // namespace
 
 hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t st) {
     if (a.Wd <= 0 || a.Hd <= 0) return hipErrorInvalidValue;
     const int rows = (a.Hd + kTileH - 1) / kTileH;
     const dim3 grid((a.Wd + kTileW - 1) / kTileW, rows < 65535 ? rows : 65535);
-    switch (a.format) {
-    case BMFR_FORMAT_F32X3: launch<BMFR_FORMAT_F32X3>(a, grid, st); break;
-    case BMFR_FORMAT_F16X4: launch<BMFR_FORMAT_F16X4>(a, grid, st); break;
-    case BMFR_FORMAT_UNORM8X4: launch<BMFR_FORMAT_UNORM8X4>(a, grid, st); break;
-    case BMFR_FORMAT_UNORM8X3: launch<BMFR_FORMAT_UNORM8X3>(a, grid, st); break;
-    case BMFR_FORMAT_UNORM10X3A2: launch<BMFR_FORMAT_UNORM10X3A2>(a, grid, st); break;
-    default: return hipErrorInvalidValue;
-    }
+    const bool listed = dispatch_surface_format(a.surf.format, [&](auto fmt) {
+        hipLaunchKernelGGL(upsample_kernel<decltype(fmt)::value>, grid, dim3(kTileW, kTileH), 0, st, a);
+    });
+    if (!listed) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

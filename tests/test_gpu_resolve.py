@@ -175,6 +175,39 @@ def test_unaligned_albedo_takes_the_pixel_path(gpu):
         _compare(s.host(), want, f, s.off, fmt, nan_in=True)
 
 
+def test_a_format_holds_the_same_bytes_whichever_entry_point_wrote_it(gpu):
+    """include/bmfr.h's promise, which csrc/bmfr_pixel_io.h keeps by being the
+    only encoder: one frame through bmfr_resolve_output (HDR), through
+    bmfr_upsample_output at ratio 1 (unguided, HDR, the frame's own albedo as
+    the display albedo: the first tap has weight 1, the rest 0) and through
+    bmfr_display_taa (reset, fed the tight F32X3 HDR resolve) leaves the same
+    surface byte for byte in every format.  65 x 47: resolve's groups, heads
+    and tails, and a partial 64-wide tile in the other two; bgr, flip_y, an
+    origin inside a larger surface with a padded pitch; alpha 0.5, so that the
+    alpha lane of the 8-, 10- and 16-bit formats is neither empty nor full.  The
+    resolve's surface is itself held to the restatement."""
+    W, H, alpha, origin = 65, 47, 0.5, (5, 3)
+    den, albedo = _untiled(W, H, 0)
+    current = Surface(rn.F32X3, W, H, 0, 0)
+    den.resolve(current.tensor, source="hdr", albedo=albedo)
+    result = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    guides = {"width": W, "height": H, "albedo": albedo}
+    kw = dict(origin=origin, flip_y=True, bgr=True, alpha=alpha)
+    for fmt, f in rn.FORMATS.items():
+        pad = {rn.UNORM8X3: 1, rn.F16X4: 8}.get(f, 4)
+        resolved, upsampled, displayed = (Surface(f, W + 8, H + 8, pad, 0) for _ in range(3))
+        den.resolve(resolved.tensor, source="hdr", albedo=albedo, **kw)
+        den.upsample(upsampled.tensor, guides, source="hdr", **kw)
+        den.display_taa(current.tensor, result, reset=True, dst=displayed.tensor, **kw)
+        want = rn.place(resolved.expected(), resolved.off, resolved.pitch, f,
+                        rn.encode(_values(W, H, "hdr"), f, True, alpha), (0, 0, W, H), H, origin, True)
+        _compare(resolved.host(), want, f, resolved.off, (fmt, "resolve"), nan_in=True)
+        want = resolved.host()
+        _compare(upsampled.host(), want, f, resolved.off, (fmt, "upsample"), nan_in=True)
+        _compare(displayed.host(), want, f, resolved.off, (fmt, "display_taa"), nan_in=True)
+    assert den.frame_status() == 0
+
+
 # -------------------------------------------------------------- tiled cases --
 @functools.lru_cache(maxsize=None)
 def _untiled_surfaces(W, H):
